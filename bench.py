@@ -6,6 +6,10 @@ A / A_adjoint GB/s against the HBM roofline.
     python bench.py --gpus 1 --steps 2 --warmup 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR
+
+`--dump-outputs DIR` writes what the timed steps computed in their last step (the gathered reconstruction of each timed leg) as
+DIR/<name>.npy in float32, at most 64 MB in all; the inputs are seeded, so two builds can be compared output for output.
 
 A "step" = one full 50-iteration PnP-PGD reconstruction of the global batch (inputs already
 resident in HBM).  The headline leg (`value`) runs the denoiser with fp32 multiplies on the fp32 matrix
@@ -23,9 +27,6 @@ import math
 import os
 import sys
 import time
-
-# (deepinv_amd sets the same default at import; bench.py touches the device before it imports the package)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")    # hardware queues for the streams of the batch lanes beside RCCL's: deepinv_amd/__init__.py
 
 import torch
 import torch.distributed as dist
@@ -86,7 +87,11 @@ def main():
     ap.add_argument("--loop-graph", action="store_true",
                     help="replay the PGD iteration as a HIP graph also on one GPU (optim/fixed_point.py: use_graph; always on for "
                          "--gpus > 1); the per-launch HIP events of `roofline` then come from one eager step after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's reconstruction of each timed leg to DIR/<name>.npy (float32, <= 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_worker:
         return cpu_worker(args.cpu_worker)
 
@@ -202,6 +207,9 @@ def main():
     denoiser.conv_precision = "fp32"
     out, elapsed, conv_prof = timed(args.warmup, args.steps)
     assert torch.isfinite(out).all()
+    dumps = {}      # name -> host copy of what the timed path returned in its last step (taken before another leg reuses buffers)
+    if args.dump_outputs and rank == 0:
+        dumps["reconstruction"] = out.detach().float().cpu()
     package = power_samples[0]
     split_leg = None
     if not args.no_split_leg:
@@ -209,6 +217,8 @@ def main():
         n2 = max(2, args.steps // 4)
         out2, el2, prof2 = timed(1, n2)
         denoiser.conv_precision = "fp32"
+        if args.dump_outputs and rank == 0:
+            dumps["reconstruction_bf16split"] = out2.detach().float().cpu()
         k2, p2 = max(prof2.items(), key=lambda kv: kv[1]["ms"])
         split_leg = {"value_bf16split": round(args.batch * n2 / el2, 4), "ms_per_step_bf16split": round(el2 / n2 * 1e3, 2),
                      "steps_bf16split": n2,
@@ -376,8 +386,27 @@ def main():
             ug = unit_gain_parity(dinv, model, denoiser, y, physics, args.iters)
             if ug:
                 res["parity_unit_gain_50it"] = ug
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dumps)
         print(json.dumps(res))
     ctx.__exit__(None, None, None)
+
+
+DUMP_BUDGET = 64 * 1000 * 1000     # bytes of array data over all files of --dump-outputs
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy in float32 per array.  An array larger than its share of DUMP_BUDGET is replaced by a fixed sample of its
+    elements (flattened, seeded, in index order), the same sample for the same shape in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET // max(len(arrays), 1) - 4096       # (room for the .npy header)
+    for name, t in arrays.items():
+        keep = share // t.element_size()
+        if t.numel() > keep:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), t.numpy().astype(np.float32, copy=False))
 
 
 class PowerSampler:

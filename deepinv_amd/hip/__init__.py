@@ -210,10 +210,10 @@ def fft_plan_host_table(n: int) -> torch.Tensor:
 # --------------------------------------------------------------------------- batch lanes
 # (device index, n) -> the n HIP streams on which independent parts of a batch run concurrently, or None when concurrent lanes were
 # measured NOT to pay on this device in this process (models/drunet.py: DRUNet._calibrated_lane_streams decides, once).  One set per
-# process: HIP multiplexes the streams of a process onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by default; this package asks
-# for 8 at import), and two lanes whose streams share a queue run one after the other - 400 ms per step at 4 slices where one
-# lane takes 327 and two overlapping lanes 302 (profiles/r06_lanes_hw_queues.txt).  Which streams share a queue depends on what
-# else the process created before (RCCL, graph capture, user code), so the choice is made by timing the real launch sequence.
+# process: HIP multiplexes the streams of a process onto a few hardware queues (GPU_MAX_HW_QUEUES), and two lanes whose streams
+# share a queue run one after the other - 400 ms per step at 4 slices where one lane takes 327 and two overlapping lanes 302
+# (profiles/r06_lanes_hw_queues.txt).  Which streams share a queue depends on what else the process created before (RCCL, graph
+# capture, user code), so the choice is made by timing the real launch sequence.
 _LANE_STREAMS: dict = {}
 
 

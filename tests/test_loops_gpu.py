@@ -553,8 +553,7 @@ def test_lane_streams_are_calibrated_by_timing(dev):
         print("lane calibration:", cal)
         assert float((out - ref).norm() / ref.norm()) < 1e-5
         st = H._LANE_STREAMS[key]
-        # at 8 slices of 320 x 320 two overlapping lanes are 10-15 % faster than one sequence: with GPU_MAX_HW_QUEUES = 8 (set by the
-        # package at import) a pair that overlaps is found
+        # at 8 slices of 320 x 320 two overlapping lanes are 10-15 % faster than one sequence: a pair that overlaps is found
         assert st is not None and len(st) == 2 and cal["lanes_ms"] < cal["one_sequence_ms"]
         assert den._calibrated_lane_streams(x, 0.05, 2) is st      # no second calibration
         H._LANE_STREAMS[key] = None                                # a refused set: one lane, same result
