@@ -1,2 +1,3 @@
 from .base import Denoiser, Reconstructor
 from .drunet import DRUNet
+from .tv import TVDenoiser, TVL1Denoiser

@@ -1,7 +1,7 @@
 from .potential import Potential
 from .distance import Distance, L2Distance
 from .data_fidelity import DataFidelity, L2, ZeroFidelity
-from .prior import Prior, PnP, ZeroPrior
+from .prior import Prior, PnP, ZeroPrior, TVPrior, TVL1Prior
 from .optim_iterators import (OptimIterator, fStep, gStep, PGDIteration, HQSIteration)
 from .fixed_point import FixedPoint
 from .optimizers import BaseOptim, PGD, HQS, optim_builder, create_iterator, BacktrackingConfig

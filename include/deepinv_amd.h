@@ -35,7 +35,7 @@ typedef void* dinv_stream_t; /* hipStream_t */
 /* library / error                                                            */
 /* ------------------------------------------------------------------------- */
 const char* dinv_last_error(void);
-int dinv_version(void);   /* 9 = this header (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
+int dinv_version(void);   /* 10 = this header (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
 /* number of visible HIP devices (0 when no GPU): used by the host to fail loudly */
 int dinv_device_count(int* count);
 
@@ -521,6 +521,51 @@ int dinv_cdiv_real(int64_t n, int64_t period, const float* s, const float* d, fl
  * x and out may alias. */
 int dinv_mask_solve(int32_t mode, int64_t n, int64_t period, const float* x, const float* m, float add, float* out,
                     dinv_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
+/* Total variation (deepinv/models/tv.py:5-240, deepinv/optim/prior.py:485-612) */
+/* ------------------------------------------------------------------------- */
+/* fp32 only.  An image is [planes, D, H, W] contiguous (planes = batch * channels; D = 1 and nd = 2 for 2-D images, nd = 3
+ * for volumes), a gradient field [planes, D, H, W, nd] with the component last ((h, w) or (d, h, w)): the reference's
+ * layout of TVDenoiser.u2.  Forward differences with a zero last row / column / slice; n * nd must stay below 2^31.
+ *
+ * One over-relaxed Chambolle-Pock iteration of TVDenoiser.forward (tv.py:131-148), two launches on `stream`:
+ *   x  = (x2 - tau nabla^T u2 + tau y) / (1 + tau)
+ *   u  = P(u2 + sigma nabla(2 x - x2))      aniso = 0: P(v) = v / max(|v|_2 / lam_b, 1) over the components (tv.py:79-84)
+ *                                           aniso = 1: P(v) = clamp(v, -lam_b, lam_b) per component (TVL1Denoiser, tv.py:239-240)
+ *   x2 += rho (x - x2),  u2 += rho (u - u2)
+ * lam[batch] is the per-sample threshold, sigma = 1 / tau / 2^(nd + 1) at the caller (tv.py:119-121).
+ * Ping-pong: (xa, ua) and (xb, ub) hold the iterate; which pair is current is state[1] & 1, state[1] being the number of
+ * iterations run so far, and the iteration writes the other pair (the +1 neighbours of a pixel read the old values).
+ * The pairs must be distinct and must not alias y.  The launch also writes 2 * dinv_tv_cp_partials(n) floats of `partial`
+ * (per-workgroup |x2_prev - x2|^2, |x2 + 1e-12|^2); a one-workgroup launch sums them in fixed order (bit-reproducible)
+ * and applies the STOPPING RULE of tv.py:141-148 over the whole batch (not per sample):
+ *   rel_err = |x2_prev - x2|_2 / |x2 + 1e-12|_2;  state[1] += 1;  state[0] = 1 if (iteration index > 1 && rel_err < crit).
+ * Once state[0] is set both launches are no-ops, so iterations enqueued after convergence leave the result exactly as the
+ * reference's `break` does: the answer is pair state[1] & 1.  The caller zeroes state (int32[2]) before the first iteration.
+ * WARM RESTART (tv.py:104-117) is the caller's: the first call on a denoiser starts from x2 = y, u2 = 0, later calls of the
+ * same shape from the stored x2 / u2.
+ * Byte model per iteration: x2, y, u2 read and x2, u2 written = (3 + 2 nd) * 4 bytes per pixel (28 in 2-D, 36 in 3-D);
+ * the neighbour values each thread recomputes are L2 hits. */
+int32_t dinv_tv_cp_partials(int64_t n);
+int dinv_tv_cp_iter(int32_t nd, int32_t batch, int32_t channels, int32_t D, int32_t H, int32_t W, float* xa, float* xb,
+                    float* ua, float* ub, const float* y, const float* lam, int32_t aniso, float tau, float sigma, float rho,
+                    float crit, float* partial, int32_t* state, dinv_stream_t stream);
+/* out = nabla x, [planes, D, H, W, nd]: out[p, k] = x[p + e_k] - x[p], 0 on the last face of axis k (tv.py:154-184).
+ * out must not alias x. */
+int dinv_tv_nabla(int32_t nd, int64_t planes, int32_t D, int32_t H, int32_t W, const float* x, float* out, dinv_stream_t stream);
+/* out = nabla^T v, the exact adjoint of dinv_tv_nabla (tv.py:186-218; components on the last face are ignored).
+ * out must not alias v. */
+int dinv_tv_nabla_adjoint(int32_t nd, int64_t planes, int32_t D, int32_t H, int32_t W, const float* v, float* out,
+                          dinv_stream_t stream);
+/* out = nabla^T (nabla x / |nabla x|_2), 0 where |nabla x| = 0: TVPrior.grad in one launch (prior.py:554-582; TVL1Prior
+ * inherits it).  Each output recomputes the normalised gradients it reads.  out must not alias x. */
+int dinv_tv_grad(int32_t nd, int64_t planes, int32_t D, int32_t H, int32_t W, const float* x, float* out, dinv_stream_t stream);
+/* out[b] = sum over sample b of |nabla x|_2 (mode 0, TVPrior.fn, prior.py:504-518) or |nabla x|_1 (mode 1, TVL1Prior.fn,
+ * prior.py:597-612); deterministic two-stage reduction, `partial` is scratch of batch * dinv_tv_fn_blocks(n / batch) floats. */
+int32_t dinv_tv_fn_blocks(int64_t per_sample);
+int dinv_tv_fn(int32_t nd, int32_t mode, int32_t batch, int32_t channels, int32_t D, int32_t H, int32_t W, const float* x,
+               float* out, float* partial, dinv_stream_t stream);
 
 #ifdef __cplusplus
 }
