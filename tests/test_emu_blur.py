@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import emu_lib as E
+from fft_cases import BLURFFT_FLAGS, _symbol_ref
 
 
 class ConvDesc(ctypes.Structure):
@@ -140,34 +141,6 @@ def test_conv3d_transpose_and_filter_grad_emulated(mode, shape):
     dk = torch.full((B, C, fd, fh, fw), float("nan"))
     E.check(l.dinv_conv3d_filter_grad(ctypes.byref(d), E.p(x), E.p(v), E.p(dk), None))
     assert float((dk.double() - kp.grad).norm() / kp.grad.norm()) < 2e-6
-
-
-def _symbol_ref(X, m, a, flags, add):
-    """SYMBOL of include/deepinv_amd.h (dinv_blurfft_apply) in fp64 with the reference's expressions (blur.py:639-657,
-    forward.py:1080-1117, 1212-1252): X complex [P,H,Wh], m real pairs [Ps,H,Wh,2], a complex [Ps,H,Wh]"""
-    P, Ps = X.shape[0], m.shape[0]
-    m = m.double().repeat(P // Ps, 1, 1, 1)
-    a = a.to(torch.complex128).repeat(P // Ps, 1, 1)
-    v = X.to(torch.complex128)
-    if flags & 1:
-        v = v * torch.conj(a)
-    v = torch.view_as_real(v)
-    mode = (flags >> 4) & 7
-    if mode == 1:
-        v = m * v
-    elif mode == 2:
-        v = m * m * v
-    elif mode == 3:
-        v = v / (m * m + add)
-    elif mode == 4:
-        v = v * torch.where(m > 1e-5, 1 / m, torch.zeros_like(m))
-    v = torch.view_as_complex(v.contiguous())
-    if flags & 2:
-        v = v * a
-    return v
-
-
-BLURFFT_FLAGS = [0x10 | 2, 1 | 0x10, 0x20, 1 | 0x20 | 2, 0x30, 1 | 0x40, 0]
 
 
 @pytest.mark.parametrize("H,W,Ps", [(64, 32, 3), (64, 64, 1), (16, 24, 3), (12, 10, 6), (128, 20, 2)])
