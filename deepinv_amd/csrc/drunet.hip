@@ -44,6 +44,7 @@ struct Conv3Args {
     // ndz = 3 depth taps, tap dz reading the input shifted by dz - 1 slices (dz_stride floats per slice); ndz = 1: plain 2-D
     int32_t ndz, depth_s;
     int64_t dz_stride;
+    const float* bias;  // BIAS instantiations: one float per (zero-padded) cout, added before ReLU / residual (DnCNN)
 };
 
 // frame pixels, pixels past the end and (3-D) the two padding slices of every volume are written as exact zeros
@@ -56,7 +57,7 @@ __device__ __forceinline__ bool writes_value(const Conv3Args& a, int64_t p) {
     return true;
 }
 
-template <int MREP, bool RELU, int NRES>
+template <int MREP, bool RELU, int NRES, bool BIAS = false>
 __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3Args a) {
     constexpr int MT = 32 * MREP;
     __shared__ __attribute__((aligned(16))) float xs[3 * SEG * LP];
@@ -161,8 +162,8 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3Args a) {
     for (int n = 0; n < 2; ++n) {
         const int64_t p = p0 + wv * 64 + n * 32 + l31;
         if (p >= a.g.np) continue;
-        store_tile<MREP, RELU, NRES>(acc, n, a.g.sl + p, writes_value(a, p), cb0, a.cblocks_valid, a.g.cs, lhi, a.y, a.res1,
-                                     a.res2);
+        store_tile<MREP, RELU, NRES, BIAS>(acc, n, a.g.sl + p, writes_value(a, p), cb0, a.cblocks_valid, a.g.cs, lhi, a.y,
+                                           a.res1, a.res2, a.bias);
     }
 }
 
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3Args a) {
 // D: pixel = lane & 15, couts 4q .. 4q+3 = one 16-byte store into channel block q >> 1.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <bool RELU, int NRES>
+template <bool RELU, int NRES, bool BIAS = false>
 __global__ __launch_bounds__(256) void conv3_thin_kernel(Conv3Args a) {
     constexpr int MT = 16;
     __shared__ __attribute__((aligned(16))) float xs[3 * SEG * LP];
@@ -250,6 +251,7 @@ __global__ __launch_bounds__(256) void conv3_thin_kernel(Conv3Args a) {
         if (p >= a.g.np) continue;
         const int64_t o = ((int64_t)cb * a.g.cs + a.g.sl + p) * 8 + 4 * (lq & 1);
         float4 v = make_float4(acc[n][0], acc[n][1], acc[n][2], acc[n][3]);
+        if (BIAS) v = add4(v, ld4(a.bias + 4 * lq));
         if (RELU) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
         if (NRES == 1) v = add4(v, ld4(a.res1 + o));
         if (NRES == 2) {     // res1 is a GATE (the forward pass's ReLU output): ReLU backward in the data-gradient convolution's epilogue
@@ -479,7 +481,7 @@ extern "C" int dinv_act_geom_init(int32_t batch, int32_t height, int32_t width, 
 
 static int conv3_launch(const dinv_act_geom* g, const float* x, const float* x2, const float* w_packed, int32_t cin,
                         int32_t cout, int32_t cout_valid, int32_t cout_tile, float* y, const float* res1, const float* res2,
-                        int32_t relu, int32_t depth, dinv_stream_t stream) {
+                        int32_t relu, int32_t depth, dinv_stream_t stream, const float* bias = nullptr) {
     if (int e = check_geom(g)) return e;
     DINV_REQUIRE(x && w_packed && y, "null tensor pointer");
     DINV_REQUIRE(cin % KC == 0 && cin >= KC, "cin=%d must be a positive multiple of %d (pad with zero channels)", cin, KC);
@@ -496,13 +498,28 @@ static int conv3_launch(const dinv_act_geom* g, const float* x, const float* x2,
     const int tpx = (ntiles + 7) / 8;
     const int ytiles = cout / cout_tile;
     Conv3Args a{make_geom(*g), x, x2, w_packed, y, res1, res2, cin, cbv, relu, ntiles, ytiles, tpx,
-                depth > 0 ? 3 : 1, depth > 0 ? depth + 2 : 0, g->plane * 8};
+                depth > 0 ? 3 : 1, depth > 0 ? depth + 2 : 0, g->plane * 8, bias};
     const unsigned gx = (unsigned)(8 * tpx * ytiles);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int nres = (res1 ? 1 : 0) + (res2 ? 1 : 0);
     DINV_REQUIRE(res1 || !res2, "res2 given without res1");
     const dim3 grid(gx);
-    if (gate) {
+    if (bias) {     // DnCNN layers: relu(conv + b), conv + b (+res1)
+        DINV_REQUIRE(!gate && !x2 && !res2 && !(relu && res1), "bias: ReLU or one residual, no x2 / res2 / gate");
+        if (thin) {
+            if (relu) hipLaunchKernelGGL((conv3_thin_kernel<true, 0, true>), grid, dim3(256), 0, s, a);
+            else if (res1) hipLaunchKernelGGL((conv3_thin_kernel<false, 1, true>), grid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((conv3_thin_kernel<false, 0, true>), grid, dim3(256), 0, s, a);
+        } else if (cout_tile == 64) {
+            if (relu) hipLaunchKernelGGL((conv3x3_kernel<2, true, 0, true>), grid, dim3(256), 0, s, a);
+            else if (res1) hipLaunchKernelGGL((conv3x3_kernel<2, false, 1, true>), grid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((conv3x3_kernel<2, false, 0, true>), grid, dim3(256), 0, s, a);
+        } else {
+            if (relu) hipLaunchKernelGGL((conv3x3_kernel<1, true, 0, true>), grid, dim3(256), 0, s, a);
+            else if (res1) hipLaunchKernelGGL((conv3x3_kernel<1, false, 1, true>), grid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((conv3x3_kernel<1, false, 0, true>), grid, dim3(256), 0, s, a);
+        }
+    } else if (gate) {
         DINV_REQUIRE(thin && res1 && !(relu & 1), "gate (relu bit 1): thin kernel only, with the gating activation as res1, without ReLU");
         hipLaunchKernelGGL((conv3_thin_kernel<false, 2>), grid, dim3(256), 0, s, a);
     } else if (thin) {
@@ -527,6 +544,14 @@ extern "C" int dinv_conv3x3(const dinv_act_geom* g, const float* x, const float*
                             int32_t cin, int32_t cout, int32_t cout_valid, int32_t cout_tile, float* y,
                             const float* res1, const float* res2, int32_t relu, dinv_stream_t stream) {
     return conv3_launch(g, x, x2, w_packed, cin, cout, cout_valid, cout_tile, y, res1, res2, relu, 0, stream);
+}
+
+extern "C" int dinv_conv3x3_bias(const dinv_act_geom* g, const float* x, const float* w_packed, const float* bias,
+                                 int32_t cin, int32_t cout, int32_t cout_valid, int32_t cout_tile, float* y, const float* res1,
+                                 int32_t relu, dinv_stream_t stream) {
+    DINV_REQUIRE(bias != nullptr, "null bias");
+    DINV_REQUIRE(relu == 0 || relu == 1, "relu must be 0 or 1");
+    return conv3_launch(g, x, nullptr, w_packed, cin, cout, cout_valid, cout_tile, y, res1, nullptr, relu, 0, stream, bias);
 }
 
 extern "C" int dinv_conv3x3x3(const dinv_act_geom* g, const float* x, const float* w_packed, int32_t cin, int32_t cout,

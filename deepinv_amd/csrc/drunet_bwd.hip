@@ -329,6 +329,48 @@ __global__ __launch_bounds__(256) void relu_backward_kernel(int64_t n4, const fl
     }
 }
 
+// ---- bias gradient (DnCNN, deepinv/models/dncnn.py): db[c] = sum over the interior pixels of gy[c].  Two fixed-order stages, no
+// atomics: slice s of the padded pixels, channel block z -> part[s][z][8] (thread sums its pixels tid, tid + 256, ... of the slice in
+// order, then a fixed LDS tree over the 256 threads); then one thread per channel adds the slices in slice order.  The slice count
+// depends on the geometry only, so the result is bit-reproducible on any device.
+__global__ __launch_bounds__(256) void bias_grad_part_kernel(Geom g, const float* __restrict__ gy, int64_t per_slice,
+                                                             float* __restrict__ part) {
+    __shared__ float4 red[2][256];
+    const int tid = threadIdx.x;
+    const int64_t p0 = (int64_t)blockIdx.x * per_slice, p1 = min(p0 + per_slice, g.np);
+    const float* src = gy + (int64_t)blockIdx.y * g.cs * 8;
+    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
+    for (int64_t p = p0 + tid; p < p1; p += 256) {
+        if (!interior(g, p)) continue;
+        s0 = add4(s0, ld4(src + (g.sl + p) * 8));
+        s1 = add4(s1, ld4(src + (g.sl + p) * 8 + 4));
+    }
+    red[0][tid] = s0;
+    red[1][tid] = s1;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) {
+            red[0][tid] = add4(red[0][tid], red[0][tid + w]);
+            red[1][tid] = add4(red[1][tid], red[1][tid + w]);
+        }
+        __syncthreads();
+    }
+    if (tid < 2) st4(part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * 8 + 4 * tid, red[tid][0]);
+}
+
+__global__ __launch_bounds__(256) void bias_grad_reduce_kernel(const float* __restrict__ part, int nslices, int cblocks, int c,
+                                                               int accumulate, float* __restrict__ db) {
+    const int ch = blockIdx.x * 256 + threadIdx.x;
+    if (ch >= c) return;
+    float t = 0.f;
+    for (int s = 0; s < nslices; ++s) t += part[(int64_t)s * cblocks * 8 + ch];
+    db[ch] = accumulate ? db[ch] + t : t;
+}
+
+int bias_grad_slices(const dinv_act_geom* g) {
+    return (int)std::min<int64_t>(512, std::max<int64_t>(1, ceil_div(g->np, 8192)));
+}
+
 int part_count(const dinv_act_geom* gs, int m, int n) {
     // workgroups (4 waves each) per tile: ~2 waves per SIMD over the chip, wave slices of at least 128 pixels
     const bool thin = m <= 16 && n <= 16;
@@ -419,6 +461,29 @@ extern "C" int dinv_relu_backward(int64_t n, const float* act, float* grad, dinv
     const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(n / 4, 256), 8192);
     hipLaunchKernelGGL(relu_backward_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), n / 4,
                        reinterpret_cast<const float4*>(act), reinterpret_cast<float4*>(grad));
+    DINV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" size_t dinv_bias_grad_workspace_bytes(const dinv_act_geom* g, int32_t c) {
+    if (!g || c < 1 || check_geom(g)) return 0;
+    return (size_t)bias_grad_slices(g) * ((c + 7) / 8) * 8 * sizeof(float);
+}
+
+extern "C" int dinv_bias_grad(const dinv_act_geom* g, const float* gy, int32_t c, float* db, int32_t accumulate, void* ws,
+                              size_t ws_bytes, dinv_stream_t stream) {
+    if (int e = check_geom(g)) return e;
+    DINV_REQUIRE(gy && db && ws, "null pointer");
+    DINV_REQUIRE(c >= 1, "bad channel count %d", c);
+    DINV_REQUIRE(ws_bytes >= dinv_bias_grad_workspace_bytes(g, c), "workspace too small");
+    const int ns = bias_grad_slices(g), cb = (c + 7) / 8;
+    DINV_REQUIRE(cb <= 65535, "too many channel blocks");
+    const int64_t per_slice = ceil_div(g->np, (int64_t)ns);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float* part = reinterpret_cast<float*>(ws);
+    hipLaunchKernelGGL(bias_grad_part_kernel, dim3((unsigned)ns, (unsigned)cb), dim3(256), 0, st, make_geom(*g), gy, per_slice, part);
+    DINV_CHECK_LAUNCH();
+    hipLaunchKernelGGL(bias_grad_reduce_kernel, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, st, part, ns, cb, c, accumulate, db);
     DINV_CHECK_LAUNCH();
     return 0;
 }

@@ -72,10 +72,12 @@ __device__ __forceinline__ float comp(const float4& v, int s) { return s == 0 ? 
 
 // epilogue shared by the three conv kernels: D[i][j], j = lane&31 (pixel), i = (reg&3) + 8*(reg>>2) + 4*h (cout),
 // i.e. register quad g = reg>>2 holds couts 8g+4h .. 8g+4h+3 = one float4 of channel block g.
-template <int MREP, bool RELU, int NRES>
+// BIAS (DnCNN): y = [relu](D + bias[cout]) (+res1) (+res2); bias holds one float per (zero-padded) cout
+template <int MREP, bool RELU, int NRES, bool BIAS = false>
 __device__ __forceinline__ void store_tile(const f32x16 (&acc)[MREP][2], int n, int64_t opix, bool in, int cb0,
                                            int cblocks_valid, int64_t cs, int lhi, float* __restrict__ y,
-                                           const float* __restrict__ res1, const float* __restrict__ res2) {
+                                           const float* __restrict__ res1, const float* __restrict__ res2,
+                                           const float* __restrict__ bias = nullptr) {
 #pragma unroll
     for (int m = 0; m < MREP; ++m) {
         float4 r1[4], r2[4];
@@ -93,6 +95,7 @@ __device__ __forceinline__ void store_tile(const f32x16 (&acc)[MREP][2], int n, 
         for (int g = 0; g < 4; ++g) {
             if (cb0 + 4 * m + g >= cblocks_valid) continue;
             float4 v = make_float4(acc[m][n][4 * g], acc[m][n][4 * g + 1], acc[m][n][4 * g + 2], acc[m][n][4 * g + 3]);
+            if (BIAS) v = add4(v, ld4(bias + (cb0 + 4 * m + g) * 8 + 4 * lhi));
             if (RELU) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
             if (NRES >= 1) v = add4(v, r1[g]);
             if (NRES >= 2) v = add4(v, r2[g]);

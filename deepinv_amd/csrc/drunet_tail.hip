@@ -17,9 +17,11 @@ using namespace dinv_drunet;
 namespace {
 
 // One lane produces one pixel x COUT channels; the 9 taps of neighbouring lanes hit L1 (launches beyond 65535 slices only).
-template <int COUT>
+// BR (DnCNN's out_conv(x1) + x, dinv_conv3x3_tail_bias): y = conv + bias[co] (+ res[co], the packed input image)
+template <int COUT, bool BR = false>
 __global__ __launch_bounds__(256) void tail3x3_kernel(Geom g, const float* __restrict__ x, const float* __restrict__ x2,
-                                                      const float* __restrict__ w, float* __restrict__ y, int ncb) {
+                                                      const float* __restrict__ w, float* __restrict__ y, int ncb,
+                                                      const float* __restrict__ bias = nullptr, const float* __restrict__ res = nullptr) {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;   // one pixel per lane: neighbours share cache lines
     if (p >= g.np) return;
     float acc[COUT];
@@ -44,6 +46,12 @@ __global__ __launch_bounds__(256) void tail3x3_kernel(Geom g, const float* __res
     float o4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int co = 0; co < COUT; ++co) o4[co] = acc[co];
+    if (BR) {
+        const float4 r = res ? ld4(res + (g.sl + p) * 8) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float rr[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+        for (int co = 0; co < COUT; ++co) o4[co] = o4[co] + bias[co] + rr[co];
+    }
     st4(y + (g.sl + p) * 8, make_float4(o4[0], o4[1], o4[2], o4[3]));
 }
 
@@ -70,9 +78,11 @@ __device__ __forceinline__ float lane_next(float v) {     // value of lane + 1
 // RB = output rows per wave: 8 where the launch has waves to spare (10 input rows per 8 output rows), 4 or 2 for small launches
 // (a 4-slice batch at RB = 8 is 960 waves for 1024 SIMDs - each walking 80 dependent row loads: 100 us where the two tensors
 // stream in 20)
-template <int COUT, int RB>
+template <int COUT, int RB, bool BR = false>
 __global__ __launch_bounds__(256) void tail3x3_shift_kernel(Geom g, const float* __restrict__ x, const float* __restrict__ x2,
-                                                            const float* __restrict__ w, float* __restrict__ y, int ncb, int sw) {
+                                                            const float* __restrict__ w, float* __restrict__ y, int ncb, int sw,
+                                                            const float* __restrict__ bias = nullptr,
+                                                            const float* __restrict__ res = nullptr) {
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * sw + lane;                                 // padded column of this lane
     const int rg = blockIdx.y * 4 + (threadIdx.x >> 6);                   // group of RB image rows (wave-uniform)
@@ -125,14 +135,21 @@ __global__ __launch_bounds__(256) void tail3x3_shift_kernel(Geom g, const float*
         float o4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int co = 0; co < COUT; ++co) o4[co] = acc[k][co];
+        if (BR) {
+            const float4 r = res ? ld4(res + (g.sl + p0 + (int64_t)k * g.wp) * 8) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float rr[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+            for (int co = 0; co < COUT; ++co) o4[co] = o4[co] + bias[co] + rr[co];
+        }
         st4(y + (g.sl + p0 + (int64_t)k * g.wp) * 8, make_float4(o4[0], o4[1], o4[2], o4[3]));
     }
 }
 
 }  // namespace
 
-extern "C" int dinv_conv3x3_tail(const dinv_act_geom* g, const float* x, const float* x2, const float* w_tail,
-                                 int32_t cin, int32_t cout, float* y, dinv_stream_t stream) {
+template <bool BR>
+static int tail_launch(const dinv_act_geom* g, const float* x, const float* x2, const float* w_tail, int32_t cin, int32_t cout,
+                       float* y, const float* bias, const float* res, dinv_stream_t stream) {
     if (int e = check_geom(g)) return e;
     DINV_REQUIRE(x && w_tail && y, "null tensor pointer");
     DINV_REQUIRE(cin >= 8 && cin % 8 == 0 && cout >= 1 && cout <= 4, "tail conv needs cin %% 8 == 0 and 1 <= cout <= 4 (got %d,%d)", cin, cout);
@@ -144,7 +161,7 @@ extern "C" int dinv_conv3x3_tail(const dinv_act_geom* g, const float* x, const f
         int rb = 8;
         while (rb > 2 && (int64_t)nstrip * ceil_div(g->height, rb) * g->batch < 2048) rb >>= 1;
         const dim3 rgrid((unsigned)nstrip, (unsigned)ceil_div(ceil_div(g->height, rb), 4), (unsigned)g->batch);
-#define DINV_TAIL(CO, RBV) hipLaunchKernelGGL((tail3x3_shift_kernel<CO, RBV>), rgrid, dim3(256), 0, st, gg, x, x2, w_tail, y, cin / 8, sw)
+#define DINV_TAIL(CO, RBV) hipLaunchKernelGGL((tail3x3_shift_kernel<CO, RBV, BR>), rgrid, dim3(256), 0, st, gg, x, x2, w_tail, y, cin / 8, sw, bias, res)
 #define DINV_TAIL_RB(CO) do { if (rb == 8) DINV_TAIL(CO, 8); else if (rb == 4) DINV_TAIL(CO, 4); else DINV_TAIL(CO, 2); } while (0)
         switch (cout) {
             case 1: DINV_TAIL_RB(1); break;
@@ -159,11 +176,22 @@ extern "C" int dinv_conv3x3_tail(const dinv_act_geom* g, const float* x, const f
     }
     const dim3 grid((unsigned)ceil_div(g->np, 256)), block(256);
     switch (cout) {
-        case 1: hipLaunchKernelGGL(tail3x3_kernel<1>, grid, block, 0, st, gg, x, x2, w_tail, y, cin / 8); break;
-        case 2: hipLaunchKernelGGL(tail3x3_kernel<2>, grid, block, 0, st, gg, x, x2, w_tail, y, cin / 8); break;
-        case 3: hipLaunchKernelGGL(tail3x3_kernel<3>, grid, block, 0, st, gg, x, x2, w_tail, y, cin / 8); break;
-        default: hipLaunchKernelGGL(tail3x3_kernel<4>, grid, block, 0, st, gg, x, x2, w_tail, y, cin / 8); break;
+        case 1: hipLaunchKernelGGL((tail3x3_kernel<1, BR>), grid, block, 0, st, gg, x, x2, w_tail, y, cin / 8, bias, res); break;
+        case 2: hipLaunchKernelGGL((tail3x3_kernel<2, BR>), grid, block, 0, st, gg, x, x2, w_tail, y, cin / 8, bias, res); break;
+        case 3: hipLaunchKernelGGL((tail3x3_kernel<3, BR>), grid, block, 0, st, gg, x, x2, w_tail, y, cin / 8, bias, res); break;
+        default: hipLaunchKernelGGL((tail3x3_kernel<4, BR>), grid, block, 0, st, gg, x, x2, w_tail, y, cin / 8, bias, res); break;
     }
     DINV_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int dinv_conv3x3_tail(const dinv_act_geom* g, const float* x, const float* x2, const float* w_tail,
+                                 int32_t cin, int32_t cout, float* y, dinv_stream_t stream) {
+    return tail_launch<false>(g, x, x2, w_tail, cin, cout, y, nullptr, nullptr, stream);
+}
+
+extern "C" int dinv_conv3x3_tail_bias(const dinv_act_geom* g, const float* x, const float* w_tail, const float* bias,
+                                      int32_t cin, int32_t cout, float* y, const float* res, dinv_stream_t stream) {
+    DINV_REQUIRE(bias != nullptr, "null bias");
+    return tail_launch<true>(g, x, nullptr, w_tail, cin, cout, y, bias, res, stream);
 }

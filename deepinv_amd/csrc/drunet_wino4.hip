@@ -72,6 +72,7 @@ struct W4Args {
     float* part_buf;               // [XCD 8][tail tile][part][8192 float4]
     int32_t* tickets;              // [XCD 8][tail tile], zero between launches (the last arriver resets its counter)
     FastDiv d_img, d_ntx, d_nct, d_npw;   // / (nty*ntx), / ntx, / nct, / npw
+    const float* bias;             // BIAS instantiations (DnCNN): one float per cout, added once, after the inverse transform
 #ifdef DINV_W4_TIMING
     long long* dbg;                // phase timestamps (s_memtime) of wave 0: 16 per tile, first 4 tiles of every workgroup
     int32_t stagger;               // experiment: workgroup j of an XCD starts (j % 4) * stagger / 4 cycles late (DINV_W4_STAGGER)
@@ -171,7 +172,9 @@ __device__ __forceinline__ uint4 pair(const uint2& X, const uint2& Y) { return m
 // (profiles/r05_wino4_power_cap_smi.log).  Bursts of 20-40 launches run 5-20 % faster in this form at every batch; SUSTAINED (the
 // whole DRUNet for seconds, scripts/r05/bf16x3_e2e.py) it is 1-3 % slower at 4, 8, 16 and 32 slices: energy per convolution, not
 // pipe time, is what the package limit prices.  Opt-in.
-template <int TH, int TW, bool RELU, int NRES, bool SPLIT, bool BF3 = false>
+// BIAS = true (dinv_conv3x3_winograd4_bias, DnCNN): y = relu(conv + bias[cout]); the bias joins the finished outputs - in the
+// tail split after the part that arrives last has added the partials, so every output gets it exactly once.
+template <int TH, int TW, bool RELU, int NRES, bool SPLIT, bool BF3 = false, bool BIAS = false>
 __global__ __launch_bounds__(NTHR) DINV_W4_ATTR
 void conv3x3_wino4_kernel(W4Args a) {
     using S = Shape4<TH, TW>;
@@ -516,6 +519,7 @@ void conv3x3_wino4_kernel(W4Args a) {
         const int fl = te & 63, ft8 = fl >> 3, fj = (fl >> 1) & 3, fh = fl & 1;
         const int cblk_r = wave, c2r = wave >> 2, gr = wave & 3;
         const int64_t cbo = ((int64_t)ect * 8 + cblk_r) * xcs;           // channel block this wave finishes
+        const int bco = (ect * 8 + cblk_r) * 8 + 4 * fh;                 // BIAS: first of the thread's four couts
         const int erd = (((c2r * 4) * 4 + gr) * 4 * 64 + ft8 * 8 + ((2 * fj + fh + ft8) & 7)) * 4;   // + (qq * 16 + it) * 256 floats
         const int wt8 = l31 & 7;
         const int ewr = ((wave * 16 + (l31 >> 3)) * 64 + wt8 * 8) * 4;    // + g * 1024 + ((2 j + h + t8) & 7) * 4 floats
@@ -637,6 +641,7 @@ void conv3x3_wino4_kernel(W4Args a) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     float4 val = o[i];
+                    if (BIAS) val = add4(val, ld4(a.bias + bco));
                     if (RELU) val = make_float4(fmaxf(val.x, 0.f), fmaxf(val.y, 0.f), fmaxf(val.z, 0.f), fmaxf(val.w, 0.f));
                     if (NRES) val = add4(val, rv[it][i]);
                     emit(it, i, val);
@@ -689,6 +694,7 @@ void conv3x3_wino4_kernel(W4Args a) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         float4 val = yo[it][i];
+                        if (BIAS) val = add4(val, ld4(a.bias + bco));
                         if (RELU) val = make_float4(fmaxf(val.x, 0.f), fmaxf(val.y, 0.f), fmaxf(val.z, 0.f), fmaxf(val.w, 0.f));
                         if (NRES) val = add4(val, ld4_so(a.res + cbo, out_off(it, i), 0u));     // (tail tiles only: latency not hidden)
                         emit(it, i, val);
@@ -713,7 +719,7 @@ LastSplit& last_split() {
     return v;
 }
 
-template <int TH, int TW, bool RELU, int NRES, bool BF3>
+template <int TH, int TW, bool RELU, int NRES, bool BF3, bool BIAS = false>
 int launch_shape(W4Args a, hipStream_t st) {
     using S = Shape4<TH, TW>;
     a.nty = (int32_t)ceil_div(a.g.h / 4, TH);
@@ -730,7 +736,7 @@ int launch_shape(W4Args a, hipStream_t st) {
     a.d_nct = make_fastdiv((uint32_t)a.nct);
     const size_t shm = S::LDSF * sizeof(float) + 16;   // + the ticket word of the tail split
     static std::atomic<uint64_t> configured{0};   // per instantiation: bit d = attribute set on device d
-    auto kern = conv3x3_wino4_kernel<TH, TW, RELU, NRES, false, BF3>;
+    auto kern = conv3x3_wino4_kernel<TH, TW, RELU, NRES, false, BF3, BIAS>;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return fail(3, "hipGetDevice failed");
     const uint64_t bit = 1ull << (dev & 63);
@@ -756,7 +762,7 @@ int launch_shape(W4Args a, hipStream_t st) {
         DINV_CHECK_LAUNCH();
     }
     if (a.split_f > 1) {
-        auto kern_s = conv3x3_wino4_kernel<TH, TW, RELU, NRES, true, BF3>;
+        auto kern_s = conv3x3_wino4_kernel<TH, TW, RELU, NRES, true, BF3, BIAS>;
         static std::atomic<uint64_t> configured_s{0};
         if (!(configured_s.load(std::memory_order_relaxed) & bit)) {
             if (hipFuncSetAttribute((const void*)kern_s, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
@@ -770,7 +776,7 @@ int launch_shape(W4Args a, hipStream_t st) {
     return 0;
 }
 
-template <bool RELU, int NRES, bool BF3>
+template <bool RELU, int NRES, bool BF3, bool BIAS = false>
 int launch_any(const W4Args& a, hipStream_t st) {
     const int tyn = a.g.h / 4, txn = a.g.w / 4;
     // rectangle shape with the least padded-tile waste; ties go to the largest rectangle (fewest halo loads)
@@ -782,9 +788,9 @@ int launch_any(const W4Args& a, hipStream_t st) {
         if (w < bw * 0.999) { bw = w; best = i; }
     }
     switch (best) {
-        case 0: return launch_shape<4, 8, RELU, NRES, BF3>(a, st);
-        case 1: return launch_shape<4, 4, RELU, NRES, BF3>(a, st);
-        default: return launch_shape<2, 2, RELU, NRES, BF3>(a, st);
+        case 0: return launch_shape<4, 8, RELU, NRES, BF3, BIAS>(a, st);
+        case 1: return launch_shape<4, 4, RELU, NRES, BF3, BIAS>(a, st);
+        default: return launch_shape<2, 2, RELU, NRES, BF3, BIAS>(a, st);
     }
 }
 
@@ -811,7 +817,7 @@ extern "C" int dinv_conv3x3_winograd4_last_split(int32_t* split_f, int32_t* n_ta
 
 static int winograd4_any(bool bf3, const dinv_act_geom* g, const float* x, const float* w_wino4, int32_t cin,
                                       int32_t cout, float* y, const float* res1, int32_t relu, void* workspace,
-                                      size_t workspace_bytes, dinv_stream_t stream) {
+                                      size_t workspace_bytes, dinv_stream_t stream, const float* bias = nullptr) {
     if (check_geom(g)) return 1;
     DINV_REQUIRE(x && w_wino4 && y, "null pointer");
     DINV_REQUIRE(cin >= 16 && cin % 16 == 0 && cout >= 64 && cout % 64 == 0,
@@ -822,7 +828,7 @@ static int winograd4_any(bool bf3, const dinv_act_geom* g, const float* x, const
     DINV_REQUIRE(g->cs * 32 < (1ll << 32), "winograd F(4,3) conv: one channel block must stay below 4 GB (32-bit buffer offsets)");
     W4Args a{};
     a.g = make_geom(*g);
-    a.x = x; a.w = w_wino4; a.y = y; a.res = res1;
+    a.x = x; a.w = w_wino4; a.y = y; a.res = res1; a.bias = bias;
     a.ncb = cin / 8; a.nct = cout / 64;
     if (workspace) {
         DINV_REQUIRE(workspace_bytes >= dinv_conv3x3_winograd4_workspace_bytes(), "winograd F(4,3) conv: workspace too small");
@@ -834,6 +840,11 @@ static int winograd4_any(bool bf3, const dinv_act_geom* g, const float* x, const
     a.stagger = getenv("DINV_W4_STAGGER") ? atoi(getenv("DINV_W4_STAGGER")) : 0;
 #endif
     hipStream_t st = (hipStream_t)stream;
+    if (bias) {
+        DINV_REQUIRE(!bf3 && !res1, "winograd F(4,3) conv with bias: fp32 form, no residual");
+        if (relu) return launch_any<true, 0, false, true>(a, st);
+        return launch_any<false, 0, false, true>(a, st);
+    }
     if (bf3) {
         if (relu) return launch_any<true, 0, true>(a, st);
         if (res1) return launch_any<false, 1, true>(a, st);
@@ -854,4 +865,11 @@ extern "C" int dinv_conv3x3_winograd4_bf16x3(const dinv_act_geom* g, const float
                                              int32_t cout, float* y, const float* res1, int32_t relu, void* workspace,
                                              size_t workspace_bytes, dinv_stream_t stream) {
     return winograd4_any(true, g, x, static_cast<const float*>(w_wino4x3), cin, cout, y, res1, relu, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dinv_conv3x3_winograd4_bias(const dinv_act_geom* g, const float* x, const float* w_wino4, const float* bias,
+                                           int32_t cin, int32_t cout, float* y, int32_t relu, void* workspace,
+                                           size_t workspace_bytes, dinv_stream_t stream) {
+    DINV_REQUIRE(bias != nullptr, "null bias");
+    return winograd4_any(false, g, x, w_wino4, cin, cout, y, nullptr, relu, workspace, workspace_bytes, stream, bias);
 }

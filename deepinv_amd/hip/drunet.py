@@ -42,7 +42,8 @@ def _l():
         l.dinv_act_unpack.argtypes = [G, vp, i32, vp, vp]
         l.dinv_conv3x3.argtypes = [G, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]
         l.dinv_conv3x3_tail.argtypes = [G, vp, vp, vp, i32, i32, vp, vp]
-        l.dinv_conv3x3_winograd.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp]
+        if hasattr(l, "dinv_conv3x3_winograd"):     # (not part of the host emulation build, tests/emu/Makefile)
+            l.dinv_conv3x3_winograd.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp]
         l.dinv_conv3x3_winograd4.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp, ctypes.c_size_t, vp]
         l.dinv_conv3x3_winograd4_bf16x3.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp, ctypes.c_size_t, vp]
         l.dinv_conv3x3_winograd4_workspace_bytes.restype = ctypes.c_size_t
@@ -65,6 +66,12 @@ def _l():
         l.dinv_conv_wgrad_3d.argtypes = [G, G, vp, i32, vp, i32, vp, i32, vp, ctypes.c_size_t, i32, i32, vp]
         l.dinv_conv_wgrad_3x3x3.argtypes = [G, vp, i32, vp, i32, ctypes.c_int64, vp, i32, vp, ctypes.c_size_t, vp]
         l.dinv_conv_up2x2.argtypes = [G, G, vp, vp, vp, i32, i32, vp, vp]
+        l.dinv_conv3x3_bias.argtypes = [G, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp]
+        l.dinv_conv3x3_winograd4_bias.argtypes = [G, vp, vp, vp, i32, i32, vp, i32, vp, ctypes.c_size_t, vp]
+        l.dinv_conv3x3_tail_bias.argtypes = [G, vp, vp, vp, i32, i32, vp, vp, vp]
+        l.dinv_bias_grad_workspace_bytes.restype = ctypes.c_size_t
+        l.dinv_bias_grad_workspace_bytes.argtypes = [G, i32]
+        l.dinv_bias_grad.argtypes = [G, vp, i32, vp, i32, vp, ctypes.c_size_t, vp]
         _declared = True
     return l
 
@@ -99,6 +106,26 @@ def pack_tail_weight(w: torch.Tensor) -> torch.Tensor:
     if cout > 4 or cin % 8:
         raise ValueError(f"tail packing needs cout <= 4 and cin % 8 == 0, got {cout},{cin}")
     return w.detach().float().reshape(cout, cin // 8, 8, 9).permute(1, 3, 0, 2).contiguous()
+
+
+def pack_thin_weight(w: torch.Tensor) -> tuple[torch.Tensor, int]:
+    """OIHW [Cout<=16, Cin, 3, 3] -> the one 16-wide cout tile of the thin-layer kernel (dinv_conv3x3 / dinv_conv3x3_bias with
+    cout_tile = 16): [1][Cin/8][9 taps][16][8], zero padded.  Returns (packed, cin_p)."""
+    cout, cin = w.shape[:2]
+    if cout > 16:
+        raise ValueError(f"thin packing needs cout <= 16, got {cout}")
+    cin_p = (cin + 7) // 8 * 8
+    wp = torch.zeros((16, cin_p, 3, 3), device=w.device, dtype=torch.float32)
+    wp[:cout, :cin] = w.detach().float()
+    return wp.reshape(1, 16, cin_p // 8, 8, 9).permute(0, 2, 4, 1, 3).contiguous(), cin_p
+
+
+def pack_bias(b: torch.Tensor | None, cout_p: int, device=None) -> torch.Tensor:
+    """bias [Cout] -> fp32 [cout_p], zero padded (what the bias epilogues read: one float per padded output channel)"""
+    out = torch.zeros(cout_p, device=device if b is None else b.device, dtype=torch.float32)
+    if b is not None:
+        out[:b.shape[0]] = b.detach().float()
+    return out
 
 
 def _pack_split_weight(w: torch.Tensor) -> torch.Tensor:
@@ -603,3 +630,56 @@ def conv_wgrad_3d(gs, gl, s, m, l, n, depth_s, dz):
     check(_l().dinv_conv_wgrad_3d(ctypes.byref(gs), ctypes.byref(gl), ptr(s), m, ptr(l), n, ptr(dw), 0, ptr(ws), ws.numel(), depth_s,
                                   dz, stream_ptr(s.device)))
     return dw
+
+
+# ---- DnCNN (models/dncnn.py): the same convolutions with a bias in the epilogue
+def conv3x3_bias(g, x, wpk, bias, cin, cout, y, cout_valid=None, res1=None, relu=False):
+    """y = relu(conv3x3(x) + bias) or conv3x3(x) + bias (+res1) on the direct fp32 kernel; wpk from pack_conv3x3_weight (MT = 32 / 64)
+    or pack_thin_weight (cout = 16); bias from pack_bias (cout floats)"""
+    mt = int(wpk.shape[3])
+    if _prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    check(_l().dinv_conv3x3_bias(ctypes.byref(g), ptr(x), ptr(wpk), ptr(bias), cin, cout, cout if cout_valid is None else cout_valid,
+                                 mt, ptr(y), ptr(res1), int(relu), stream_ptr(y.device)))
+    if _prof is not None:
+        e1.record()
+        fl = 2.0 * 9 * cin * (cout if cout_valid is None else cout_valid) * g.batch * g.height * g.width
+        _prof.append((e0, e1, "conv3_thin_kernel" if mt == 16 else "conv3x3_kernel", fl, 2.0 * 9 * cin * cout * g.np))
+
+
+def conv3x3_winograd4_bias(g, x, wino4, bias, cin, cout, y, relu=False, workspace=None):
+    """y = [relu](conv3x3(x) + bias) via Winograd F(4x4,3x3) (csrc/drunet_wino4.hip, bias in the epilogue); wino4 from
+    pack_winograd4_weight; height and width multiples of 4"""
+    if _prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    check(_l().dinv_conv3x3_winograd4_bias(ctypes.byref(g), ptr(x), ptr(wino4), ptr(bias), cin, cout, ptr(y), int(relu),
+                                           ptr(workspace), 0 if workspace is None else workspace.numel(), stream_ptr(y.device)))
+    if _prof is not None:
+        e1.record()
+        tiles = g.batch * (g.height // 4) * (g.width // 4)
+        _prof.append((e0, e1, "conv3x3_wino4_kernel", 2.0 * 9 * cin * cout * g.batch * g.height * g.width,
+                      2.0 * 36 * cin * cout * tiles))
+
+
+def conv3x3_tail_bias(g, x, wtail, bias, cin, cout, y, res=None):
+    """last layer on the vector ALU: y[:cout] = conv3x3(x) + bias (+ res, first channel block); wtail from pack_tail_weight"""
+    if _prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    check(_l().dinv_conv3x3_tail_bias(ctypes.byref(g), ptr(x), ptr(wtail), ptr(bias), cin, cout, ptr(y), ptr(res), stream_ptr(y.device)))
+    if _prof is not None:
+        e1.record()
+        fl = 2.0 * 9 * cin * cout * g.batch * g.height * g.width
+        _prof.append((e0, e1, "tail3x3_shift_kernel", fl, 0.0))
+
+
+def bias_grad(g, gy, c, db=None, accumulate=False):
+    """db[ch] (+)= sum of gy[ch] over the interior pixels, ch < c (csrc/drunet_bwd.hip: fixed-order, deterministic); returns db [c]"""
+    if db is None:
+        db = torch.empty(c, device=gy.device, dtype=torch.float32)
+        accumulate = False
+    ws = torch.empty(_l().dinv_bias_grad_workspace_bytes(ctypes.byref(g), c), device=gy.device, dtype=torch.uint8)
+    check(_l().dinv_bias_grad(ctypes.byref(g), ptr(gy), c, ptr(db), int(accumulate), ptr(ws), ws.numel(), stream_ptr(gy.device)))
+    return db

@@ -35,7 +35,7 @@ typedef void* dinv_stream_t; /* hipStream_t */
 /* library / error                                                            */
 /* ------------------------------------------------------------------------- */
 const char* dinv_last_error(void);
-int dinv_version(void);   /* 10 = this header (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
+int dinv_version(void);   /* 11 = this header (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
 /* number of visible HIP devices (0 when no GPU): used by the host to fail loudly */
 int dinv_device_count(int* count);
 
@@ -161,6 +161,11 @@ int dinv_conv3x3x3(const dinv_act_geom* g, const float* x, const float* w_packed
  * w_tail: [cin/8][9 taps][cout][8]; cin % 8 == 0. */
 int dinv_conv3x3_tail(const dinv_act_geom* g, const float* x, const float* x2, const float* w_tail, int32_t cin,
                       int32_t cout, float* y, dinv_stream_t stream);
+/* DnCNN's last layer on the same vector-ALU kernel: y[first channel block, channels 0..cout-1] = conv3x3(x) + bias (+ res)
+ * (out_conv(x1) + x, deepinv/models/dncnn.py): bias of cout floats, res (may be NULL) an activation buffer whose first channel
+ * block holds the residual (the packed input image); 1 <= cout <= 4, cin % 8 == 0, w_tail as for dinv_conv3x3_tail. */
+int dinv_conv3x3_tail_bias(const dinv_act_geom* g, const float* x, const float* w_tail, const float* bias, int32_t cin,
+                           int32_t cout, float* y, const float* res, dinv_stream_t stream);
 /* Same operator as dinv_conv3x3 (no x2, one optional residual) through Winograd F(2x2,3x3): 2.25x fewer MFMA
  * flops, results equal up to fp32 rounding of the transforms (~1e-6 relative).
  * w_wino: U = G g G^T per (cout, cin), packed [cout/64][cin/8][ci 8][co 64][16]; cin % 16 == 0, cin >= 32,
@@ -195,6 +200,21 @@ int dinv_conv3x3_winograd4(const dinv_act_geom* g, const float* x, const float* 
 int dinv_conv3x3_winograd4_bf16x3(const dinv_act_geom* g, const float* x, const void* w_wino4x3, int32_t cin, int32_t cout,
                                   float* y, const float* res1, int32_t relu, void* workspace, size_t workspace_bytes,
                                   dinv_stream_t stream);
+/* ---- DnCNN (deepinv/models/dncnn.py: 3x3 convolutions WITH bias, ReLU between them, out_conv(x1) + x) on the same kernels,
+ * the bias fused into the epilogues.  `bias` is device memory holding one float per (zero-padded) output channel.
+ * Direct fp32 kernel of dinv_conv3x3: y = relu(conv3x3(x) + bias) (relu = 1) or conv3x3(x) + bias (+res1) (relu = 0), stride 1,
+ * zero padding 1; w_packed / cout / cout_valid / cout_tile as for dinv_conv3x3, cout_tile = 16 (cout padded to 16) selects the
+ * thin-layer kernel; bias has cout floats.  Any height and width (DnCNN's head, and the body layers the Winograd form does not
+ * take: H or W not a multiple of 4, or cout not a multiple of 64). */
+int dinv_conv3x3_bias(const dinv_act_geom* g, const float* x, const float* w_packed, const float* bias, int32_t cin,
+                      int32_t cout, int32_t cout_valid, int32_t cout_tile, float* y, const float* res1, int32_t relu,
+                      dinv_stream_t stream);
+/* dinv_conv3x3_winograd4 with a bias: y = [relu](conv3x3(x) + bias), no residual, bias of cout floats added after the inverse
+ * transform (with the tail split: once, by the part that adds the partial outputs - the result stays deterministic); same
+ * packing, shape rules and workspace as dinv_conv3x3_winograd4 (DnCNN's body layers). */
+int dinv_conv3x3_winograd4_bias(const dinv_act_geom* g, const float* x, const float* w_wino4, const float* bias, int32_t cin,
+                                int32_t cout, float* y, int32_t relu, void* workspace, size_t workspace_bytes,
+                                dinv_stream_t stream);
 /* What the calling thread's last dinv_conv3x3_winograd4 did with its incomplete last round: the number of parts each tail tile
  * was cut into (1 = not cut) and the tail tiles per XCD (tests and diagnostics; either pointer may be NULL). */
 int dinv_conv3x3_winograd4_last_split(int32_t* split_f, int32_t* n_tail_tiles);
@@ -263,6 +283,12 @@ size_t dinv_conv_wgrad_workspace_bytes(const dinv_act_geom* gs, int32_t m, int32
 int dinv_conv_wgrad(const dinv_act_geom* gs, const dinv_act_geom* gl, const float* s, int32_t m, const float* l,
                     int32_t n, int32_t taps, float* dw, int32_t accumulate, void* ws, size_t ws_bytes,
                     dinv_stream_t stream);
+/* Bias gradient of a convolution (DnCNN training): db[ch] (+)= sum over the interior pixels of gy[ch], ch < c, gy in the padded
+ * channel-blocked layout.  Deterministic: per-slice partial sums in `ws` (dinv_bias_grad_workspace_bytes(g, c) bytes; the
+ * slice count depends on the geometry only), added in a fixed order, no atomics.  accumulate != 0 adds to db. */
+size_t dinv_bias_grad_workspace_bytes(const dinv_act_geom* g, int32_t c);
+int dinv_bias_grad(const dinv_act_geom* g, const float* gy, int32_t c, float* db, int32_t accumulate, void* ws,
+                   size_t ws_bytes, dinv_stream_t stream);
 /* grad <- grad where act > 0 else 0 (ReLU backward on whole activation buffers; n floats, n % 4 == 0) */
 int dinv_relu_backward(int64_t n, const float* act, float* grad, dinv_stream_t stream);
 
