@@ -2,3 +2,4 @@ from .base import Denoiser, Reconstructor
 from .drunet import DRUNet
 from .tv import TVDenoiser, TVL1Denoiser
 from .dncnn import DnCNN
+from .tgv import TGVDenoiser

@@ -35,7 +35,7 @@ typedef void* dinv_stream_t; /* hipStream_t */
 /* library / error                                                            */
 /* ------------------------------------------------------------------------- */
 const char* dinv_last_error(void);
-int dinv_version(void);   /* 11 = this header (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
+int dinv_version(void);   /* 12 = this header (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
 /* number of visible HIP devices (0 when no GPU): used by the host to fail loudly */
 int dinv_device_count(int* count);
 
@@ -592,6 +592,53 @@ int dinv_tv_grad(int32_t nd, int64_t planes, int32_t D, int32_t H, int32_t W, co
 int32_t dinv_tv_fn_blocks(int64_t per_sample);
 int dinv_tv_fn(int32_t nd, int32_t mode, int32_t batch, int32_t channels, int32_t D, int32_t H, int32_t W, const float* x,
                float* out, float* partial, dinv_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
+/* Total generalized variation (deepinv/models/tgv.py:7-310)                 */
+/* ------------------------------------------------------------------------- */
+/* fp32 only.  Images x2 and y are [planes, D, H, W] contiguous (planes = batch * channels; D = 1 and nd = 2 for 2-D images,
+ * nd = 3 for volumes), the auxiliary field r2 [planes, D, H, W, nd] and the dual u2 [planes, D, H, W, nd^2], component
+ * last: the reference's layouts of TGVDenoiser.r2 and .u2.  Component i * nd + j of u2 pairs field component i with spatial
+ * axis j ((h, w) or (d, h, w)).  nabla is TV's forward difference (zero on the last face), epsilon a backward difference per
+ * component, zero on the first face: eps(v)[p, i nd + j] = v_i(p) - v_i(p - e_j).  n * nd^2 must stay below 2^31.
+ *
+ * One over-relaxed Chambolle-Pock iteration of TGVDenoiser.forward (tgv.py:148-171), three launches on `stream`:
+ *   t  = tau eps^T(u2)
+ *   x  = (x2 - nabla^T t + tau y) / (1 + tau)
+ *   r  = s - s / max(|s|_2 / (tau lam1_b), 1),  s = r2 + t            (over the nd components, tgv.py:76-83)
+ *   u  = P(u2 + sigma eps(nabla(2x - x2) - (2r - r2)))                 P(v) = v / max(|v|_2 / lam2_b, 1) over the nd^2
+ *   x2 += rho (x - x2),  r2 += rho (r - r2),  u2 += rho (u - u2)           components (tgv.py:85-91)
+ * lam1[batch] = 0.1 ths_b and lam2[batch] = 0.15 ths_b are the per-sample weights; sigma = 1 / tau / (72 f) with f = 1 in 2-D
+ * and 3 in 3-D at the caller (tgv.py:121-146).  ths_b > 0 is the contract: the reference returns NaN at ths = 0 and this
+ * library does not reproduce it.
+ * Ping-pong: (xa, ra, ua) and (xb, rb, ub) hold the iterate; which set is current is state[1] & 1, state[1] being the
+ * number of iterations run so far, and the iteration writes the other set.  The sets must be distinct and must not alias
+ * y.  z (n floats) and w (n * nd floats) are scratch that carries 2x - x2 and 2r - r2 from the primal launch to the dual
+ * one.  In 2-D ua, ub, ra, rb and w must be 16-byte aligned.  The launch also writes 2 * dinv_tgv_cp_partials(n) floats
+ * of `partial` (per-workgroup |x2_prev - x2|^2, |x2|^2); a one-workgroup launch sums them in fixed order (bit-reproducible)
+ * and applies the STOPPING RULE of tgv.py:162-171 over the whole batch (not per sample):
+ *   rel_err = |x2_prev - x2|_2 / (|x2|_2 + 1e-12);  state[1] += 1;  state[0] = 1 if (iteration index > 1 && rel_err < crit).
+ * (TV divides by |x2 + 1e-12|_2 instead.)  Once state[0] is set all three launches are no-ops, so iterations enqueued after
+ * convergence leave the result exactly as the reference's `break` does: the answer is set state[1] & 1.  The caller zeroes
+ * state (int32[2]) before the first iteration.
+ * WARM RESTART (tgv.py:107-119) is the caller's: the first call on a denoiser starts from x2 = y, r2 = 0, u2 = 0, later
+ * calls of the same shape from the stored x2 / r2 / u2.
+ * Byte model per iteration, per pixel (the neighbour reads are L1 / L2 hits):
+ *   primal launch  x2, y, r2, u2 read, x2', r2', z, w written: (2 + nd + nd^2) + (2 + 2 nd) floats
+ *   dual launch    z, w, u2 read, u2' written:                 (1 + nd + nd^2) + nd^2 floats
+ *   total (5 + 4 nd + 3 nd^2) * 4 bytes: 100 in 2-D, 176 in 3-D. */
+int32_t dinv_tgv_cp_partials(int64_t n);
+int dinv_tgv_cp_iter(int32_t nd, int32_t batch, int32_t channels, int32_t D, int32_t H, int32_t W, float* xa, float* xb,
+                     float* ra, float* rb, float* ua, float* ub, const float* y, const float* lam1, const float* lam2, float tau,
+                     float sigma, float rho, float crit, float* z, float* w, float* partial, int32_t* state,
+                     dinv_stream_t stream);
+/* out = eps(v), [planes, D, H, W, nd^2] from v [planes, D, H, W, nd] (tgv.py:230-271).  out must not alias v. */
+int dinv_tgv_epsilon(int32_t nd, int64_t planes, int32_t D, int32_t H, int32_t W, const float* v, float* out,
+                     dinv_stream_t stream);
+/* out = eps^T(u), [planes, D, H, W, nd] from u [planes, D, H, W, nd^2]: the exact adjoint of dinv_tgv_epsilon
+ * (tgv.py:273-310; components on the first face of their axis are ignored).  out must not alias u. */
+int dinv_tgv_epsilon_adjoint(int32_t nd, int64_t planes, int32_t D, int32_t H, int32_t W, const float* u, float* out,
+                             dinv_stream_t stream);
 
 #ifdef __cplusplus
 }
