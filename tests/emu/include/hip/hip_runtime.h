@@ -196,8 +196,10 @@ inline void wave_exchange_end() {
 }
 }  // namespace emu
 
+// every launch is recorded by the spelling of its kernel expression (launch_log.cpp): the tests assert which kernel a call reached
+extern "C" void dinv_emu_log_launch(const char* kernel);
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    ::emu::launch(kernel, dim3(grid), dim3(block), (size_t)(shmem), __VA_ARGS__)
+    (::dinv_emu_log_launch(#kernel), ::emu::launch(kernel, dim3(grid), dim3(block), (size_t)(shmem), __VA_ARGS__))
 // dynamic LDS: `extern __shared__ T name[];` on the device
 #define DINV_DYN_LDS(T, name) T* name = reinterpret_cast<T*>(::emu::g.dynsmem.data())
 

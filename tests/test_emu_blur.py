@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import emu_lib as E
+from conv_cases import _ref_conv, _ref_conv3
 from fft_cases import BLURFFT_FLAGS, _symbol_ref
 
 
@@ -18,24 +19,6 @@ class ConvDesc(ctypes.Structure):
 
 
 MODES = {"valid": 0, "circular": 1, "reflect": 2, "replicate": 3, "constant": 4}
-
-
-def _ref_conv(x, k, mode, stride):
-    """true convolution (flipped filter) of the padded image, deepinv's `conv2d` (convolution.py:42-107), then [::s, ::s]"""
-    B, C, H, W = x.shape
-    fh, fw = k.shape[-2:]
-    x, k = x.double(), k.double().expand(-1, C, -1, -1) if k.shape[1] != C else k.double()
-    if mode != "valid":
-        ph, pw = fh // 2, fw // 2
-        pad = (pw, pw - (1 - fw % 2), ph, ph - (1 - fh % 2))       # deepinv pads ih = (h-1)//2 .. : the odd / even split below
-        pad = ((fw - 1) // 2, fw // 2, (fh - 1) // 2, fh // 2)
-        x = torch.nn.functional.pad(x, pad, mode=mode if mode != "constant" else "constant", value=0)
-    out = []
-    for b in range(B):
-        kb = k[b if k.shape[0] > 1 else 0]
-        out.append(torch.nn.functional.conv2d(x[b:b + 1], torch.flip(kb, (-2, -1))[:, None], groups=C))
-    y = torch.cat(out, 0)
-    return y[:, :, ::stride, ::stride]
 
 
 @pytest.mark.parametrize("mode", ["valid", "circular", "reflect", "replicate", "constant"])
@@ -99,18 +82,6 @@ def test_rfft2_irfft2_emulated(H, W):
 class Conv3dDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("batch", "channels", "depth", "height", "width", "fbatch", "fchannels", "fd", "fh", "fw",
                                               "mode", "reserved")]
-
-
-def _ref_conv3(x, k, mode):
-    """true 3-D convolution of the padded volume, deepinv's conv3d (convolution.py:333-393)"""
-    B, C = x.shape[:2]
-    fd, fh, fw = k.shape[-3:]
-    if mode != "valid":
-        pad = ((fw - 1) // 2, fw // 2, (fh - 1) // 2, fh // 2, (fd - 1) // 2, fd // 2)
-        x = torch.nn.functional.pad(x, pad, mode=mode if mode != "constant" else "constant", value=0)
-    k = k.expand(B, C, fd, fh, fw)
-    out = torch.nn.functional.conv3d(x.reshape(1, B * C, *x.shape[2:]), torch.flip(k, (-3, -2, -1)).reshape(B * C, 1, fd, fh, fw), groups=B * C)
-    return out.reshape(B, C, *out.shape[2:])
 
 
 @pytest.mark.parametrize("mode", ["valid", "circular", "reflect", "replicate", "constant"])
