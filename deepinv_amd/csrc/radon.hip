@@ -28,6 +28,18 @@ struct RadonGeom {
     float scale;  // 1/operator_norm (tomography.py:253-254)
 };
 
+// the disc mask of radon.py:270-283, xa^2 + ya^2 <= 1, with both squares rounded before the sum as the reference's tensor
+// expression rounds them: the squares are made opaque so that the compiler cannot contract the sum into a fused multiply-add,
+// which moves points that lie on the circle outside it (row 56, column 7 of a 71 x 71 disc: 0.6^2 + 0.8^2 rounds to 1 in fp32,
+// fma(0.6, 0.6, 0.8^2) to 1 + 2^-23)
+__device__ __forceinline__ bool in_unit_disc(float xa, float ya) {
+    float x2 = xa * xa, y2 = ya * ya;
+#ifndef DINV_EMU
+    asm volatile("" : "+v"(x2), "+v"(y2));
+#endif
+    return x2 + y2 <= 1.0f;
+}
+
 // sample position (ix -> column, iy -> row) for grid = [gx, gy] R^T (radon.py:334-341), unnormalised as ATen's grid_sampler
 // (align_corners=True): the fan-beam kernels, whose lattice is not uniform
 __device__ __forceinline__ void sample_pos(float c, float s, float xj, float xi, float gm1, float& ix, float& iy) {
@@ -69,7 +81,7 @@ __global__ void radon_pack_image(RadonGeom g, const float* __restrict__ x, float
             // radon.py:270-283: mask = (xax^2 + yax^2 <= 1), axes = 2*k/(W-1) - 1
             const float ya = 2.0f * (float)c / (float)(g.W - 1) - 1.0f;
             const float xa = 2.0f * (float)r / (float)(g.W - 1) - 1.0f;
-            in = (xa * xa + ya * ya) <= 1.0f;
+            in = in_unit_disc(xa, ya);
         }
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
@@ -166,7 +178,7 @@ __global__ __launch_bounds__(256) void radon_adj_kernel(RadonGeom g, const float
     if (g.circle) {
         const float ya = 2.0f * (float)col / (float)(g.W - 1) - 1.0f;
         const float xa = 2.0f * (float)row / (float)(g.W - 1) - 1.0f;
-        live = (xa * xa + ya * ya) <= 1.0f;
+        live = in_unit_disc(xa, ya);
     }
     if (live) {
         for (int a = 0; a < g.A; ++a) {
@@ -308,7 +320,7 @@ __global__ __launch_bounds__(256) void radon_fan_adj_kernel(RadonGeom g, int n_d
     if (g.circle) {
         const float ya = 2.0f * (float)col / (float)(g.W - 1) - 1.0f;
         const float xa = 2.0f * (float)row / (float)(g.W - 1) - 1.0f;
-        live = (xa * xa + ya * ya) <= 1.0f;
+        live = in_unit_disc(xa, ya);
     }
     if (live) {
         for (int a = 0; a < g.A; ++a) {
@@ -371,7 +383,7 @@ __global__ __launch_bounds__(256) void iradon_kernel(RadonGeom g, const float* _
     const float gm1 = (float)(g.G - 1);
     const float* sn = sino + (int64_t)n * g.G * g.A;
     float acc = 0.f;
-    const bool live = !g.circle || (xg * xg + yg * yg <= 1.0f);
+    const bool live = !g.circle || in_unit_disc(xg, yg);
     if (live) {
         for (int a = 0; a < g.A; ++a) {
             const float t = xg * cs_s[a].x - yg * cs_s[a].y;   // _XYtoT (radon.py:458-461)

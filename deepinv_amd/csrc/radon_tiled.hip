@@ -64,6 +64,18 @@ struct TiledGeom {
     float scale;
 };
 
+// the disc mask of radon.py:270-283, xa^2 + ya^2 <= 1, with both squares rounded before the sum as the reference's tensor
+// expression rounds them: the squares are made opaque so that the compiler cannot contract the sum into a fused multiply-add,
+// which moves points that lie on the circle outside it (row 56, column 7 of a 71 x 71 disc: 0.6^2 + 0.8^2 rounds to 1 in fp32,
+// fma(0.6, 0.6, 0.8^2) to 1 + 2^-23)
+__device__ __forceinline__ bool in_unit_disc(float xa, float ya) {
+    float x2 = xa * xa, y2 = ya * ya;
+#ifndef DINV_EMU
+    asm volatile("" : "+v"(x2), "+v"(y2));
+#endif
+    return x2 + y2 <= 1.0f;
+}
+
 // identical to radon.hip (see the note there): sample position (ix -> column, iy -> row) of lattice point (j, i) of the rotated
 // uniform grid, (ix, iy) = ctr + R (j - ctr, i - ctr): a per-ray base and one fused multiply-add per coordinate and step
 __device__ __forceinline__ void ray_base(float c, float s, float dj, float ctr, float& bx, float& by) {
@@ -103,7 +115,7 @@ __global__ void radon_pack_image2(TiledGeom g, const float* __restrict__ x, floa
         if (in && g.circle) {   // radon.py:270-283 (symmetric in r and c)
             const float ya = 2.0f * (float)c / (float)(g.W - 1) - 1.0f;
             const float xa = 2.0f * (float)r / (float)(g.W - 1) - 1.0f;
-            in = in_t = (xa * xa + ya * ya) <= 1.0f;
+            in = in_t = in_unit_disc(xa, ya);
         }
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
@@ -356,7 +368,7 @@ __global__ __launch_bounds__(256) void radon_adj_tiled_kernel(TiledGeom g, const
     if (live && g.circle) {
         const float ya = 2.0f * (float)col / (float)(g.W - 1) - 1.0f;
         const float xa = 2.0f * (float)row / (float)(g.W - 1) - 1.0f;
-        live = (xa * xa + ya * ya) <= 1.0f;
+        live = in_unit_disc(xa, ya);
     }
     float acc[NB];
 #pragma unroll

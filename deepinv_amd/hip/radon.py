@@ -150,6 +150,8 @@ def _adj(y, geo: RadonGeometry, norm, scale=1.0):
         check(_l().dinv_radon_adjoint_tiled(ctypes.byref(d), ptr(y), ptr(geo.xn), ptr(geo.cs), _norm_ptr(norm, dev), ptr(x),
                                             ptr(ws), ws.numel(), stream_ptr(dev)))
         return x
+    # the gather adjoint keeps (cos, sin) of every angle in LDS behind G words: 4 * (G rounded up to even) + 8 * A <= 64 KiB, so
+    # above TILED_MAX_GRID it raises (no fallback) for more than 6143 angles at G = 4097, fewer at larger G
     d = geo.desc(B * C, scale)
     ws = torch.empty(_l().dinv_radon_workspace_bytes(ctypes.byref(d), 1), device=dev, dtype=torch.uint8)
     check(_l().dinv_radon_adjoint(ctypes.byref(d), ptr(y), ptr(geo.xn), ptr(geo.cs), ptr(x), ptr(ws), ws.numel(),

@@ -18,6 +18,7 @@
 #include <cstring>
 #include <functional>
 #include <vector>
+#include <typeinfo>
 
 #define DINV_EMU 1
 #ifndef __HIP_DEVICE_COMPILE__
@@ -196,10 +197,24 @@ inline void wave_exchange_end() {
 }
 }  // namespace emu
 
-// every launch is recorded by the spelling of its kernel expression (launch_log.cpp): the tests assert which kernel a call reached
+// every launch is recorded by the spelling of its kernel expression (launch_log.cpp): the tests assert which kernel a call reached.
+// Beside the spelling, the instantiation itself (template arguments resolved, from the signature of kernel_name<K>) and the block
+// size: a launcher that picks the instantiation from a runtime value spells every choice alike.  The instantiation needs a kernel
+// expression that is a constant: sources built with DINV_EMU_LOG_INSTANCES (the Makefile's list) have only such launches.
+namespace emu {
+template <auto K> struct KernelTag {};
+template <auto K> inline const char* kernel_name() { return typeid(KernelTag<K>).name(); }   // mangled, demangled by the log
+}  // namespace emu
 extern "C" void dinv_emu_log_launch(const char* kernel);
-#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    (::dinv_emu_log_launch(#kernel), ::emu::launch(kernel, dim3(grid), dim3(block), (size_t)(shmem), __VA_ARGS__))
+extern "C" void dinv_emu_log_instance(const char* signature, unsigned block);
+#ifdef DINV_EMU_LOG_INSTANCES
+#define DINV_EMU_INSTANCE(kernel) ::emu::kernel_name<kernel>()
+#else
+#define DINV_EMU_INSTANCE(kernel) #kernel
+#endif
+#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...)                                       \
+    (::dinv_emu_log_launch(#kernel), ::dinv_emu_log_instance(DINV_EMU_INSTANCE(kernel), dim3(block).x),   \
+     ::emu::launch(kernel, dim3(grid), dim3(block), (size_t)(shmem), __VA_ARGS__))
 // dynamic LDS: `extern __shared__ T name[];` on the device
 #define DINV_DYN_LDS(T, name) T* name = reinterpret_cast<T*>(::emu::g.dynsmem.data())
 

@@ -21,18 +21,9 @@ class FftPlan(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("radix", ctypes.c_int32 * MAX_STAGES)]
 
 
-class RadonDesc(ctypes.Structure):
-    _fields_ = [("n_img", ctypes.c_int32), ("width", ctypes.c_int32), ("grid", ctypes.c_int32),
-                ("pad_before", ctypes.c_int32), ("n_angles", ctypes.c_int32), ("circle", ctypes.c_int32),
-                ("scale", ctypes.c_float), ("reserved", ctypes.c_int32)]
-
-
-class RadonPlan(ctypes.Structure):
-    _fields_ = [("grid", ctypes.c_int32), ("n_angles", ctypes.c_int32), ("kw", ctypes.c_int32), ("band_h", ctypes.c_int32),
-                ("win_w", ctypes.c_int32), ("n_jblocks", ctypes.c_int32), ("n_bands", ctypes.c_int32),
-                ("n_chunks_plain", ctypes.c_int32), ("n_chunks_swap", ctypes.c_int32), ("fits", ctypes.c_int32),
-                ("blob_words", ctypes.c_int32), ("widest_window", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)]
-
+from radon_cases import RadonDesc, RadonPlan  # noqa: E402,F401  (the structures of include/deepinv_amd.h)
+from radon_cases import RadonGeom as _RadonTables  # noqa: E402
+from radon_cases import FanGeom as _FanTables  # noqa: E402
 
 _lib = None
 
@@ -67,38 +58,13 @@ def p(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
-class RadonGeom:
-    """the host tables exactly as deepinv_amd.hip.radon.RadonGeometry builds them"""
-
-    def __init__(self, angles_deg, width, circle):
-        sqrt2 = (2 * torch.ones(1)).sqrt()
-        self.W = int(width)
-        if circle:
-            self.G, self.pad = self.W, 0
-        else:
-            self.G = int((sqrt2 * self.W).ceil())
-            pad = int((sqrt2 * self.W - self.W).ceil())
-            self.pad = (self.W + pad) // 2 - self.W // 2
-        self.circle = bool(circle)
-        a = torch.as_tensor(angles_deg, dtype=torch.float32)
-        theta = a * 4 * torch.ones(1).atan() / 180
-        self.A = int(a.numel())
-        self.cs = torch.stack([theta.cos(), theta.sin()], dim=1).contiguous()
-        self.xn = torch.linspace(-1, 1, self.G).contiguous()
-
-    def desc(self, n_img, scale=1.0):
-        return RadonDesc(n_img, self.W, self.G, self.pad, self.A, int(self.circle), float(scale), 0)
+class RadonGeom(_RadonTables):
+    """the host tables exactly as deepinv_amd.hip.radon.RadonGeometry builds them, planned by the emulated library"""
 
     def plan(self, n_img, kw=0):
         """kw = 1, 2, 4, 8 forces the angles per workgroup (dinv_radon_plan_init reads plan.kw on entry), 0 = automatic"""
-        l = lib()
-        d = self.desc(n_img)
-        nbytes = l.dinv_radon_plan_bytes(ctypes.byref(d))
-        blob = np.zeros(nbytes // 4, np.int32)
-        pl = RadonPlan()
-        pl.kw = kw
-        check(l.dinv_radon_plan_init(ctypes.byref(d), p(self.cs), ctypes.byref(pl), p(blob)))
-        return pl, blob
+        pl, blob = self.plan_host(lib(), n_img, kw)
+        return pl, blob.numpy()
 
 
 def radon_forward_tiled(x, geo, norm=None, scale=1.0, kw=0):
@@ -158,16 +124,8 @@ def ramp_fft(y):
     return out
 
 
-class FanGeom(RadonGeom):
+class FanGeom(_FanTables):
     """fan-beam tables from the product's own host code (deepinv_amd.hip.radon.fan_tables: pure torch)"""
-
-    def __init__(self, angles_deg, width, circle, fan_parameters=None):
-        super().__init__(angles_deg, width, circle)
-        import sys
-        sys.path.insert(0, os.path.dirname(HERE))
-        from deepinv_amd.hip.radon import fan_tables
-        self.fp, self.xm, self.sc, self.yd = fan_tables(self.G, self.W, fan_parameters)
-        self.n_det = int(self.yd.numel())
 
 
 def radon_fan_forward(x, geo):
