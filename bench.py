@@ -1,20 +1,27 @@
 #!/usr/bin/env python
 """Headline benchmark (BASELINE.json): PnP-PGD slices/sec (50 iterations) on 2-D 8-coil
-320x320 MRI with a 4x radial mask and the DRUNet(2->2) denoiser, global batch 32, plus
+320x320 MRI with a 4x radial mask and the DRUNet(2->2) denoiser, global batch 32, plus (with --full)
 A / A_adjoint GB/s against the HBM roofline.
 
     python bench.py --gpus 1 --steps 2 --warmup 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full
+
+A plain run sets up, warms up, times the steps of the headline leg and prints its line: `value`, `ms_per_step`, `dtype` and the
+`roofline` of the dominant kernel (from HIP events of the timed steps themselves).  `--full` adds everything that takes runs of its
+own: the bf16-split companion leg, the operator rows and the loops of the other configurations, the per-layer errors against fp64,
+the CPU baseline and the parity figures (`--no-split-leg`, `--no-other-configs`, `--no-cpu-baseline` leave parts of it out).
 
 `--dump-outputs DIR` writes what the timed steps computed in their last step (the gathered reconstruction of each timed leg) as
-DIR/<name>.npy in float32, at most 64 MB in all; the inputs are seeded, so two builds can be compared output for output.
+DIR/<name>.npy in float32, at most 64 MB in all; the inputs are seeded, so two builds can be compared output for output.  The
+bf16-split leg's reconstruction is written in every run (a plain run computes it in one untimed step for the purpose).
 
 A "step" = one full 50-iteration PnP-PGD reconstruction of the global batch (inputs already
 resident in HBM).  The headline leg (`value`) runs the denoiser with fp32 multiplies on the fp32 matrix
 cores (the reference's arithmetic type); the bf16-split throughput setting is a companion leg
-(`value_bf16split`).  Multi-GPU: the batch is sharded in contiguous slabs, one process per GPU,
+(`value_bf16split`, with --full).  Multi-GPU: the batch is sharded in contiguous slabs, one process per GPU,
 reconstructions combined by one RCCL all-gather per step (inside the timed region);
 total work is fixed as N grows ("scaling": "strong", the north_star's >=6x@8 target).
 Prints ONE JSON line on rank 0.
@@ -70,11 +77,14 @@ def main():
     ap.add_argument("--iters", type=int, default=50, help="PGD iterations per reconstruction")
     ap.add_argument("--size", type=int, default=320)
     ap.add_argument("--coils", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: the bf16-split leg, operator rows and loops of the other "
+                         "configurations, per-layer errors against fp64, the CPU baseline and the parity figures")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity figures")
     ap.add_argument("--no-split-leg", "--no-fp32-leg", dest="no_split_leg", action="store_true",
-                    help="skip the companion timing of the bf16-split throughput setting")
+                    help="skip the bf16-split throughput setting (its timing with --full, its reconstruction with --dump-outputs)")
     ap.add_argument("--cpu-worker", type=str, default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the operator rows of configs 3-5")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the operator rows of configs 3-5")
     ap.add_argument("--lanes", type=int, default=None,
                     help="DRUNet.batch_lanes: the per-GPU batch cut into this many parts, each run through the network on its own HIP "
                          "stream (models/drunet.py); default: the model's default (auto: 2 up to 16 slices of 320 x 320, else 1)")
@@ -212,7 +222,7 @@ def main():
         dumps["reconstruction"] = out.detach().float().cpu()
     package = power_samples[0]
     split_leg = None
-    if not args.no_split_leg:
+    if args.full and not args.no_split_leg:
         denoiser.conv_precision = "bf16split"
         n2 = max(2, args.steps // 4)
         out2, el2, prof2 = timed(1, n2)
@@ -231,8 +241,18 @@ def main():
                                             "direct_equiv": round(p2["direct_flops"] / (p2["ms"] * 1e-3) / 1e12, 2),
                                             "avg_launch_ms": round(p2["ms"] / max(p2["launches"], 1), 4)},
                      "rel_diff_bf16split_vs_fp32": float(f"{float((out2 - out).norm() / out.norm()):.3e}")}
+    elif args.dump_outputs and not args.no_split_leg:
+        # the companion leg's reconstruction without its timing: one untimed step in the bf16-split setting (every step reconstructs
+        # the same batch from the same measurement, so this is what the last timed step of that leg returns)
+        denoiser.conv_precision = "bf16split"
+        out2 = step()
+        fence()
+        denoiser.conv_precision = "fp32"
+        if rank == 0:
+            dumps["reconstruction_bf16split"] = out2.detach().float().cpu()
+        del out2
 
-    # ---- operator GB/s (outside the timed region)
+    # ---- operator GB/s (outside the timed region; --full)
     ops = []
     def time_op(fn, n=20):
         for _ in range(3):
@@ -272,15 +292,16 @@ def main():
                     "denoiser_TFLOP_per_s": round(gflop / t / 1e3, 1), "conv_precision": precision,
                     "finite": bool(torch.isfinite(o).all())})
 
-    alg = (B_local * 2 * H * W + B_local * 2 * args.coils * H * W) * 4 + args.coils * H * W * 8 + 2 * H * W * 4
-    op_row("MultiCoilMRI.A", "cfg2", B_local, lambda: physics.A(x_true), alg)
-    op_row("MultiCoilMRI.A_adjoint", "cfg2", B_local, lambda: physics.A_adjoint(y), alg)
-    op_row("MultiCoilMRI.A_adjoint_A", "cfg2", B_local, lambda: physics.A_adjoint_A(x_true), 2 * B_local * 2 * H * W * 4
-           + args.coils * H * W * 8 + 2 * H * W * 4)
-    if not multi:
-        blur_and_single_coil_rows(dinv, device, op_row)
-    if not multi and not args.no_other_configs:
-        other_config_ops(dinv, device, op_row, lambda: ops[-1], loop_row, ops.append)
+    if args.full:
+        alg = (B_local * 2 * H * W + B_local * 2 * args.coils * H * W) * 4 + args.coils * H * W * 8 + 2 * H * W * 4
+        op_row("MultiCoilMRI.A", "cfg2", B_local, lambda: physics.A(x_true), alg)
+        op_row("MultiCoilMRI.A_adjoint", "cfg2", B_local, lambda: physics.A_adjoint(y), alg)
+        op_row("MultiCoilMRI.A_adjoint_A", "cfg2", B_local, lambda: physics.A_adjoint_A(x_true), 2 * B_local * 2 * H * W * 4
+               + args.coils * H * W * 8 + 2 * H * W * 4)
+        if not multi:
+            blur_and_single_coil_rows(dinv, device, op_row)
+        if not multi and not args.no_other_configs:
+            other_config_ops(dinv, device, op_row, lambda: ops[-1], loop_row, ops.append)
 
     if rank == 0:
         slices_per_s = args.batch * args.steps / elapsed
@@ -370,13 +391,14 @@ def main():
                                         "one eager step after the timed region (the timed steps replay a HIP graph: no events inside it)",
                          "conv3x3_direct_equiv_TFLOPs": round(all_direct / (all_ms * 1e-3) / 1e12, 2) if all_ms else 0.0,
                          "kernels": {k: {"ms": round(v["ms"], 2), "launches": v["launches"]} for k, v in conv_prof.items()}},
-            "operators": ops,
         }
+        if args.full:
+            res["operators"] = ops
         if split_leg:
             res.update(split_leg)
-        if not multi:
+        if args.full and not multi:
             res["layer_rel_err_vs_fp64"] = layer_errors(device)
-        if not args.no_cpu_baseline and not multi:   # CPU baseline: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and not multi:   # CPU baseline: rank 0 at N=1 only
             res["cpu_baseline"] = cpu_baseline(denoiser, maps, mask, H, W, args.coils, args.iters, y_cpu=y.cpu(), x_gpu=out.cpu())
             res["parity_rel_err_50it"] = res["cpu_baseline"].pop("parity_rel_err_max")
             res["parity_slices"] = res["cpu_baseline"].pop("parity_slices")

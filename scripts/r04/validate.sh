@@ -6,7 +6,7 @@ R=gpurun_out
 mkdir -p $R
 timeout 1200 python -m pytest tests -q -m gpu > $R/r04_gpu_tests.log 2>&1; echo "tests rc=$?"; grep -E "passed|failed" $R/r04_gpu_tests.log | tail -2; grep -E "^FAILED|^ERROR" $R/r04_gpu_tests.log | head
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-timeout 600 python bench.py --steps 5 --warmup 2 > $R/r04_bench_b32.json 2> $R/r04_bench_b32.err; echo "bench rc=$?"
+timeout 600 python bench.py --full --steps 5 --warmup 2 > $R/r04_bench_b32.json 2> $R/r04_bench_b32.err; echo "bench rc=$?"
 python - <<'P'
 import json
 d=json.loads(open('gpurun_out/r04_bench_b32.json').read().strip().splitlines()[-1])

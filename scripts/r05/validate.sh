@@ -7,7 +7,7 @@ T=${1:-r05}
 mkdir -p $R
 timeout 1500 python -m pytest tests -q -m gpu -s > $R/${T}_gpu_tests.log 2>&1; echo "tests rc=$?"; grep -E "passed|failed" $R/${T}_gpu_tests.log | tail -2; grep -E "^FAILED|^ERROR" $R/${T}_gpu_tests.log | head
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-timeout 900 python bench.py --steps 5 --warmup 2 > $R/${T}_bench.json 2> $R/${T}_bench.err; echo "bench rc=$?"; tail -3 $R/${T}_bench.err
+timeout 900 python bench.py --full --steps 5 --warmup 2 > $R/${T}_bench.json 2> $R/${T}_bench.err; echo "bench rc=$?"; tail -3 $R/${T}_bench.err
 python - <<P
 import json
 d=json.loads(open('gpurun_out/${T}_bench.json').read().strip().splitlines()[-1])
@@ -18,6 +18,7 @@ for v in d['operators']:
 P
 if [ -n "$2" ]; then
   export TMPDIR=/tmp
-  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$R/${T}_bench_prof -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs > /dev/null 2>&1); echo "prof rc=$?"
+  root=$PWD
+  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $root/$R/${T}_bench_prof -o bench -- python $root/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs > /dev/null 2>&1); echo "prof rc=$?"
   python3 scripts/r05/kstats.py $(find $R/${T}_bench_prof -name "*.db" | head -1) > $R/${T}_bench_kernel_stats.txt; head -30 $R/${T}_bench_kernel_stats.txt | cut -c1-200
 fi

@@ -2,7 +2,8 @@
 cd $GRAFT_REPO_ROOT
 R=gpurun_out
 export TMPDIR=/tmp
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace -d $GRAFT_REPO_ROOT/$R/r06_ov4_prof -o b -- python $GRAFT_REPO_ROOT/bench.py --batch 4 --steps 1 --warmup 1 --iters 12 --loop-graph --no-split-leg --no-cpu-baseline --no-other-configs > /dev/null 2>&1); echo "prof rc=$?"
+root=$PWD
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace -d $root/$R/r06_ov4_prof -o b -- python $root/bench.py --full --batch 4 --steps 1 --warmup 1 --iters 12 --loop-graph --no-split-leg --no-cpu-baseline --no-other-configs > /dev/null 2>&1); echo "prof rc=$?"
 DB=$(find $R/r06_ov4_prof -name "*.db" | head -1)
 python3 scripts/r05/kstats.py $DB "wino4|conv3x3|down2x2|up2x2|tail|pack|rows|cols|lincomb" > $R/r06_b4_lanes_kernel_stats.txt; cat $R/r06_b4_lanes_kernel_stats.txt | cut -c1-190
 python3 scripts/r06/wino4_calls.py $DB | tee -a $R/r06_b4_lanes_kernel_stats.txt

@@ -8,7 +8,7 @@ timeout 600 python -m pytest tests/test_named_shapes_gpu.py -q -m gpu -s -k "dis
 timeout 300 python scripts/r06/bench_blur.py > $R/r06_b3_blur.jsonl 2>&1; cat $R/r06_b3_blur.jsonl | cut -c1-300
 run() { # name, args...
   n=$1; shift
-  timeout 600 python bench.py "$@" --steps 4 --warmup 2 --loop-graph --no-split-leg --no-cpu-baseline --no-other-configs > $R/r06_b3_$n.json 2>> $R/r06_b3_bench.err
+  timeout 600 python bench.py --full "$@" --steps 4 --warmup 2 --loop-graph --no-split-leg --no-cpu-baseline --no-other-configs > $R/r06_b3_$n.json 2>> $R/r06_b3_bench.err
   python -c "
 import json; d=json.loads(open('$R/r06_b3_$n.json').read().strip().splitlines()[-1]); print('$n', d['ms_per_step'], d['roofline']['avg_launch_ms'], d['config'].get('batch_lanes'), d['roofline']['package_during_timed_steps']['socket_power_w_median'], d['roofline']['package_during_timed_steps']['sclk_mhz_median'])"
 }

@@ -5,7 +5,7 @@ R=gpurun_out
 mkdir -p $R
 run() { # name, args...
   n=$1; shift
-  timeout 600 python bench.py "$@" --steps 4 --warmup 2 --no-split-leg --no-cpu-baseline --no-other-configs > $R/r06_b4_$n.json 2>> $R/r06_b4_bench.err
+  timeout 600 python bench.py --full "$@" --steps 4 --warmup 2 --no-split-leg --no-cpu-baseline --no-other-configs > $R/r06_b4_$n.json 2>> $R/r06_b4_bench.err
   python -c "
 import json; d=json.loads(open('$R/r06_b4_$n.json').read().strip().splitlines()[-1]); print('$n', d['ms_per_step'], d['roofline']['avg_launch_ms'], d['config'].get('batch_lanes'), d['config'].get('loop_graph'), d['roofline']['package_during_timed_steps']['socket_power_w_median'], d['roofline']['package_during_timed_steps']['sclk_mhz_median'])"
 }
@@ -22,7 +22,7 @@ run b4_l2_eager --batch 4 --lanes 2
 run b2_l2 --batch 2 --lanes 2 --loop-graph
 run b2_l1 --batch 2 --lanes 1 --loop-graph
 timeout 1500 python -m pytest tests -q -m gpu > $R/r06_b4_gpu_tests.log 2>&1; echo "suite rc=$?"; grep -E "passed|failed" $R/r06_b4_gpu_tests.log | tail -2; grep -E "^FAILED|^ERROR" $R/r06_b4_gpu_tests.log | head
-timeout 900 python bench.py --steps 3 --warmup 1 > $R/r06_b4_bench.json 2>> $R/r06_b4_bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 3 --warmup 1 > $R/r06_b4_bench.json 2>> $R/r06_b4_bench.err; echo "bench rc=$?"
 python - <<P
 import json
 d=json.loads(open('gpurun_out/r06_b4_bench.json').read().strip().splitlines()[-1])

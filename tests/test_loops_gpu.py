@@ -448,6 +448,44 @@ def test_bench_multi_gpu_code_path_preflight_on_one_rank():
     assert res["roofline"]["launches"] > 0 and "cpu_baseline" not in res
 
 
+def test_bench_plain_run_times_the_headline_leg_only_and_full_adds_the_rest(tmp_path):
+    """`bench.py` without --full: the headline leg, its line and --dump-outputs (both legs' reconstructions, the companion's from
+    one untimed step) and nothing that takes runs of its own; --full adds the companion leg, the operator rows and the per-layer
+    errors (small batch, few iterations; the CPU baseline and configs 3-5 left out)"""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "4", "--iters", "6", "--steps", "2",
+              "--warmup", "1"]
+
+    def run(*extra):
+        r = subprocess.run(common + list(extra), capture_output=True, text=True, timeout=900, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    moved = ("operators", "value_bf16split", "ms_per_step_bf16split", "layer_rel_err_vs_fp64", "cpu_baseline", "parity_rel_err_50it")
+    plain = run("--dump-outputs", str(tmp_path))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in plain, k
+    assert plain["value"] > 0 and plain["steps"] == 2 and plain["roofline"]["launches"] > 0
+    assert not [k for k in moved if k in plain]
+    assert sorted(os.listdir(tmp_path)) == ["reconstruction.npy", "reconstruction_bf16split.npy"]
+    rec, rec2 = np.load(tmp_path / "reconstruction.npy"), np.load(tmp_path / "reconstruction_bf16split.npy")
+    assert rec.shape == rec2.shape == (4, 2, 320, 320) and np.isfinite(rec2).all()
+    assert 0 < np.linalg.norm(rec2 - rec) / np.linalg.norm(rec) < 1e-5     # the same reconstruction in the other arithmetic
+
+    full = run("--full", "--no-cpu-baseline", "--no-other-configs")
+    assert full["value_bf16split"] > 0 and full["layer_rel_err_vs_fp64"]
+    assert {"MultiCoilMRI.A", "MultiCoilMRI.A_adjoint", "BlurFFT.A"} <= {r["op"] for r in full["operators"]}
+
+
 @pytest.mark.parametrize("B,lanes", [(4, 2), (5, 2), (6, 3)])
 def test_drunet_batch_lanes_equal_one_launch_sequence(dev, B, lanes):
     """DRUNet.batch_lanes (models/drunet.py): the batch cut into parts that run through the network concurrently on their own HIP
