@@ -649,6 +649,27 @@ __global__ __launch_bounds__(256) void mri_coil_combine_kernel(const float2* __r
     }
 }
 
+// coil combination of any volume, one pixel per thread (grid-stride over B * vol): the last pass of the adjoint behind the
+// in-place inverse rows pass, for row lengths whose combine tile (mri_rows_combine_kernel) does not fit the LDS.  The coil order
+// n = 0..N-1 is fixed: deterministic.
+__global__ __launch_bounds__(256) void mri_coil_combine_any_kernel(const float2* __restrict__ t, const float2* __restrict__ maps,
+                                                                   float* __restrict__ x, int64_t vol, int64_t total, int ncoil,
+                                                                   int maps_batch) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / vol, pix = i - b * vol;
+        const float2* tp = t + b * ncoil * vol + pix;
+        const float2* sp = maps ? maps + (maps_batch > 1 ? b : 0) * ncoil * vol + pix : nullptr;
+        float2 acc = make_float2(0.f, 0.f);
+        for (int n = 0; n < ncoil; ++n) {
+            float2 v = tp[(int64_t)n * vol];
+            if (sp) v = cmulc(v, sp[(int64_t)n * vol]);  // conj(S) * v
+            acc = cadd(acc, v);
+        }
+        x[b * 2 * vol + pix] = acc.x;
+        x[(b * 2 + 1) * vol + pix] = acc.y;
+    }
+}
+
 template <int N>
 int launch_cols_expand_fwd(const float* x, const float2* maps, float2* t, int64_t B, int ncoil, int maps_batch, int64_t Q,
                            const void* table, float scale, hipStream_t s) {
@@ -891,6 +912,12 @@ extern "C" int dinv_mri_adjoint(const dinv_mri_desc* d, const float* y, const fl
         // short first axis (a 3-D volume's depth): single-stage inverse transform with the coil sum in its store phase
         return launch_cols_combine_inv<16>(t, mp, x, d->batch, d->coils, d->maps_batch, Q0, d->table[0], sc0, s);
     }
+    const dinv_fft_plan& pw = d->plan[nd - 1];
+    // the rows pass below needs no more LDS than the forward's rows pass: refuse here, before anything is written, where that
+    // one refuses too.  (launch_rows' own line-count check, blocks < 2^31, can still refuse after the first pass has written t;
+    // it needs more than 2^31 rows of one length, far past any workspace this operator is given)
+    DINV_REQUIRE(fft_lds_bytes(pw, rows_lines_per_block(pw)) <= kMaxLdsBytes, "fft length %d does not fit the 160 KiB LDS tile",
+                 pw.n);
     const int64_t Na = d->dims[0];
     ColsPlanarMaskLoadIo cio{y, mask, t, d->coils, d->mask_batch, 0, 0};
     if (int e = launch_cols(cio, P, vol / Na, d->plan[0], d->table[0], 1, 1, 1.0f / sqrtf((float)Na), s)) return e;
@@ -900,9 +927,8 @@ extern "C" int dinv_mri_adjoint(const dinv_mri_desc* d, const float* y, const fl
         if (int e = launch_cols(mio, P * d->dims[0], W, d->plan[1], d->table[1], 1, 1, 1.0f / sqrtf((float)H), s)) return e;
     }
     // rows pass + coil combine
-    const dinv_fft_plan& pw = d->plan[nd - 1];
+    const float2* mp = reinterpret_cast<const float2*>(maps);
     {
-        const float2* mp = reinterpret_cast<const float2*>(maps);
         const int64_t nl = (int64_t)d->batch * R;
         const float sc = 1.0f / sqrtf((float)W);
         switch (pw.n) {
@@ -916,12 +942,23 @@ extern "C" int dinv_mri_adjoint(const dinv_mri_desc* d, const float* y, const fl
     if (lpb > 16) lpb = 16;
     const int LS = fft_line_stride(pw.n);
     const size_t lds = fft_lds_bytes(pw, lpb) + (size_t)lpb * LS * sizeof(float2);
-    DINV_REQUIRE(lds <= kMaxLdsBytes, "fft length %d does not fit the 160 KiB LDS tile", pw.n);
+    if (lds > kMaxLdsBytes) {
+        // the combine tile (FFT tile + an lpb x LS accumulator) does not fit: the in-place inverse rows pass, which has the
+        // forward's LDS limit, then a per-pixel coil combination
+        C2CIo rio{t, t, 0, 0};
+        if (int e = launch_rows(rio, P * R, pw, d->table[nd - 1], 1, 1, 1.0f / sqrtf((float)W), s)) return e;
+        const int64_t total = (int64_t)d->batch * vol;
+        const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(total, 256), 4 * kMaxGrid);
+        hipLaunchKernelGGL(mri_coil_combine_any_kernel, dim3(grid), dim3(256), 0, s, t, mp, x, vol, total, d->coils,
+                           d->maps_batch);
+        DINV_CHECK_LAUNCH();
+        return 0;
+    }
     if (int e = set_lds_limit(mri_rows_combine_kernel, lds)) return e;
     const int64_t nlines = (int64_t)d->batch * R;
     const int64_t blocks = ceil_div(nlines, lpb);
-    hipLaunchKernelGGL(mri_rows_combine_kernel, dim3((unsigned)blocks), dim3(256), lds, s, t,
-                       reinterpret_cast<const float2*>(maps), x, nlines, R, d->coils, d->maps_batch, lpb, pw,
+    hipLaunchKernelGGL(mri_rows_combine_kernel, dim3((unsigned)blocks), dim3(256), lds, s, t, mp, x, nlines, R, d->coils,
+                       d->maps_batch, lpb, pw,
                        d->table[nd - 1], 1, 1.0f / sqrtf((float)W));
     DINV_CHECK_LAUNCH();
     return 0;

@@ -9,12 +9,7 @@ import pytest
 import torch
 
 import emu_lib as E
-
-
-class MriDesc(ctypes.Structure):
-    _fields_ = [("batch", ctypes.c_int32), ("coils", ctypes.c_int32), ("ndim", ctypes.c_int32), ("dims", ctypes.c_int32 * 3),
-                ("mask_batch", ctypes.c_int32), ("maps_batch", ctypes.c_int32), ("coil_dim", ctypes.c_int32),
-                ("reserved", ctypes.c_int32), ("plan", E.FftPlan * 3), ("table", ctypes.c_void_p * 3)]
+from mri_cases import MriDesc, _cfft, _ref_adjoint, _ref_forward
 
 
 def _desc(B, N, vol, mask, maps, coil_dim=1):
@@ -24,7 +19,7 @@ def _desc(B, N, vol, mask, maps, coil_dim=1):
     for i, n in enumerate(vol):
         d.dims[i] = n
         plan, table = E.fft_plan(n)
-        d.plan[i] = plan
+        d.plan[i] = type(d.plan[i]).from_buffer_copy(plan)
         d.table[i] = table.ctypes.data
         keep.append(table)
     d.mask_batch = 0 if mask is None else mask.shape[0]
@@ -32,28 +27,6 @@ def _desc(B, N, vol, mask, maps, coil_dim=1):
     d.coil_dim = coil_dim
     d.reserved = 1      # reach the wave-autonomous 2-D pipelines (csrc/mri_wave.hpp) at these small batches too
     return d, keep
-
-
-def _cfft(z, dims, inverse=False):
-    f = torch.fft.ifftn if inverse else torch.fft.fftn
-    return torch.fft.fftshift(f(torch.fft.ifftshift(z, dim=dims), dim=dims, norm="ortho"), dim=dims)
-
-
-def _ref_forward(x, maps, mask):
-    xc = torch.complex(x[:, 0], x[:, 1]).to(torch.complex128)            # [B, vol]
-    dims = tuple(range(-(x.ndim - 2), 0))
-    k = _cfft(maps.to(torch.complex128) * xc[:, None], dims)               # [B, N, vol]
-    y = torch.stack([k.real, k.imag], 1)                                   # [B, 2, N, vol]
-    return y * mask.double()[:, :, None]
-
-
-def _ref_adjoint(y, maps, mask):
-    dims = tuple(range(-(y.ndim - 3), 0))
-    ym = y.double() * mask.double()[:, :, None]
-    k = torch.complex(ym[:, 0], ym[:, 1])
-    u = _cfft(k, dims, inverse=True)
-    xc = (maps.to(torch.complex128).conj() * u).sum(1)
-    return torch.stack([xc.real, xc.imag], 1)
 
 
 def _run(fn, d, *ptrs):

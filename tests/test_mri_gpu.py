@@ -238,3 +238,144 @@ def test_single_coil_normal_operator_and_autograd(dev):
     w = torch.randn_like(out)
     (out * w).sum().backward()
     assert rel_err(x.grad, phys.A_adjoint_A(w).detach()) < 1e-6        # self-adjoint: backward is the same chain
+
+
+# ------------------------------------------------------------------ the case table of tests/mri_cases.py on the device
+@pytest.fixture
+def runner(dev):
+    import mri_cases as K
+    from deepinv_amd import hip
+
+    return K.Runner(hip.lib(), dev, lambda: hip.stream_ptr(dev), lambda n: hip.fft_plan(n, dev), desc=hip.MriDesc)
+
+
+def _table():
+    import mri_cases as K
+
+    return K.CASES
+
+
+@pytest.mark.parametrize("case", _table(), ids=lambda c: c.id)
+def test_mri_path(runner, case):
+    """every case of the table, grid edges included: per-image error against complex128, guard bands, fully written outputs,
+    untouched inputs, bit-identical repeat calls, exact zeros under each mask channel, dot test, A^T A symmetric and == A^T(A x)"""
+    import mri_cases as K
+
+    errs = K.run_case(runner, case)
+    print(f"{case.id}: " + ", ".join(f"{op} {K.family(case, i)} {errs[op]:.3g}" for i, op in enumerate(("A", "AT", "ATA"))
+                                      if op in errs))
+
+
+def test_mri_rejections_write_nothing(runner):
+    import mri_cases as K
+
+    K.run_rejections(runner)
+
+
+def test_mri_empty_batch(runner):
+    import mri_cases as K
+
+    K.run_empty(runner)
+
+
+def _layer_errors(case, phys, x, maps, mask, v, dev):
+    """per-image errors of A, A^T and A^T A of a physics layer against complex128 (mask [mb,2,*vol])"""
+    import mri_cases as K
+
+    y = phys.A(x.to(dev)).cpu()
+    ea = K.err_forward(case, y.reshape(case.B, 2, case.N, *case.vol), x, maps, mask)
+    xa = phys.A_adjoint(v.reshape(y.shape).to(dev)).cpu()
+    eat = K.err_adjoint(case, xa, v, maps, mask)
+    xn = phys.A_adjoint_A(x.to(dev)).cpu()
+    eata = K.err_normal(case, xn, x, maps, mask)
+    assert torch.all(y.reshape(case.B, 2, case.N, *case.vol)[mask[:, :, None].expand(case.B, 2, case.N, *case.vol) == 0] == 0)
+    return ea, eat, eata
+
+
+@pytest.mark.parametrize("layer", ["multicoil", "single"])
+@pytest.mark.parametrize("mshape", ["hw", "11hw", "b2hw"])
+def test_layer_mask_shapes(dev, layer, mshape):
+    """MultiCoilMRI / MRI with masks of shape (H, W), (1, 1, H, W) and (B, 2, H, W) with distinct channels"""
+    import deepinv_amd as dinv
+    import mri_cases as K
+
+    B, img = 2, (320, 320) if layer == "multicoil" else (64, 128)
+    N = 4 if layer == "multicoil" else 1
+    g = _g(21)
+    x = torch.randn(B, 2, *img, generator=g)
+    m = torch.rand(B, 2, *img, generator=g)
+    m = torch.where(m < 0.3, torch.zeros_like(m), m + 0.25)
+    mask = {"hw": m[0, 0], "11hw": m[:1, :1], "b2hw": m}[mshape]
+    full = O.check_mask(mask).expand(-1, 2, *img).float().contiguous()
+    maps = (torch.randn(1, N, *img, dtype=torch.complex64, generator=g) / N ** 0.5) if layer == "multicoil" else None
+    v = torch.randn(B, 2, N, *img, generator=g)
+    if layer == "multicoil":
+        phys = dinv.physics.MultiCoilMRI(mask=mask, coil_maps=maps, img_size=(2, *img), device=dev)
+    else:
+        phys = dinv.physics.MRI(mask=mask, img_size=(2, *img), device=dev)
+    case = K.Case("layer", img, B, N, "none" if maps is None else "shared", "per" if full.shape[0] == B else "shared")
+    ea, eat, eata = _layer_errors(case, phys, x, maps, full, v, dev)
+    fam = "wave" if layer == "multicoil" else "static"
+    assert ea < K.BOUNDS["A-" + fam] and eat < K.BOUNDS["AT-static"] and eata < K.BOUNDS["ATA-static"], (ea, eat, eata)
+
+
+def test_layer_complex128_maps_and_noncontiguous_x(dev):
+    import deepinv_amd as dinv
+    import mri_cases as K
+
+    B, N, img = 3, 5, (128, 64)
+    g = _g(22)
+    maps = torch.randn(1, N, *img, dtype=torch.complex128, generator=g) / N ** 0.5
+    m = torch.rand(1, 2, *img, generator=g)
+    mask = torch.where(m < 0.3, torch.zeros_like(m), m)
+    big = torch.randn(B, 2, img[1], img[0], generator=g)
+    x = big.transpose(-1, -2)                                    # non-contiguous
+    assert not x.is_contiguous()
+    phys = dinv.physics.MultiCoilMRI(mask=mask, coil_maps=maps, img_size=(2, *img), device=dev)
+    v = torch.randn(B, 2, N, *img, generator=g)
+    case = K.Case("layer", img, B, N, "shared", "shared")
+    m64 = maps.to(torch.complex64)                               # the library computes with complex64 maps
+    y = phys.A(x.to(dev)).cpu()
+    assert K.err_forward(case, y, x.contiguous(), m64, mask) < K.BOUNDS["A-static"]
+    assert K.err_adjoint(case, phys.A_adjoint(v.to(dev)).cpu(), v, m64, mask) < K.BOUNDS["AT-static"]
+    assert K.err_normal(case, phys.A_adjoint_A(x.to(dev)).cpu(), x.contiguous(), m64, mask) < K.BOUNDS["ATA-static"]
+
+
+@pytest.mark.parametrize("B", [15, 16])
+def test_layer_wave_threshold(dev, B):
+    """A^T / A^T A of MultiCoilMRI switch to the wave pipelines at B * 64 >= 1024; both sides against complex128"""
+    import deepinv_amd as dinv
+    import mri_cases as K
+
+    N, img = 2, (256, 256)
+    g = _g(23)
+    x = torch.randn(B, 2, *img, generator=g)
+    maps = torch.randn(B, N, *img, dtype=torch.complex64, generator=g) / N ** 0.5
+    m = torch.rand(B, 2, *img, generator=g)
+    mask = torch.where(m < 0.3, torch.zeros_like(m), m)
+    v = torch.randn(B, 2, N, *img, generator=g)
+    phys = dinv.physics.MultiCoilMRI(mask=mask, coil_maps=maps, img_size=(2, *img), device=dev)
+    case = K.Case("layer", img, B, N, "per", "per")
+    fam = "wave" if B >= 16 else "static"
+    assert K.wave2d_ok(case, 1) == (B >= 16)
+    ea, eat, eata = _layer_errors(case, phys, x, maps, mask, v, dev)
+    assert ea < K.BOUNDS["A-wave"] and eat < K.BOUNDS["AT-" + fam] and eata < K.BOUNDS["ATA-" + fam], (ea, eat, eata)
+
+
+def test_layer_normal_at_a_width_only_the_split_adjoint_admits(dev):
+    """W = 5851 (the rows pass's limit, above the combine tile's): A, A^T and A^T A = A^T(A x) all work"""
+    import deepinv_amd as dinv
+    import mri_cases as K
+
+    B, N, img = 2, 3, (4, 5851)
+    assert K.combine_lds(img[1]) > 160 * 1024 >= K.rows_lds(img[1])
+    g = _g(24)
+    x = torch.randn(B, 2, *img, generator=g)
+    maps = torch.randn(B, N, *img, dtype=torch.complex64, generator=g) / N ** 0.5         # per-sample maps and masks
+    m = torch.rand(B, 2, *img, generator=g)
+    mask = torch.where(m < 0.3, torch.zeros_like(m), m)
+    v = torch.randn(B, 2, N, *img, generator=g)
+    phys = dinv.physics.MultiCoilMRI(mask=mask, coil_maps=maps, img_size=(2, *img), device=dev)
+    case = K.Case("layer", img, B, N, "per", "per")
+    ea, eat, eata = _layer_errors(case, phys, x, maps, mask, v, dev)
+    assert ea < K.BOUNDS["A-generic"] and eat < K.BOUNDS["AT-rows-split"] and eata < 2 * K.BOUNDS["AT-rows-split"], (ea, eat, eata)
