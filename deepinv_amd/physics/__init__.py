@@ -4,5 +4,7 @@ from .noise import NoiseModel, ZeroNoise, GaussianNoise
 from .mri import MRI, MultiCoilMRI, MRIMixin
 from .tomography import Tomography, RampFilter
 from .blur import Blur, BlurFFT, Downsampling
+from .singlepixel import SinglePixelCamera
 from . import functional
+from . import singlepixel
 from . import generator

@@ -35,7 +35,7 @@ typedef void* dinv_stream_t; /* hipStream_t */
 /* library / error                                                            */
 /* ------------------------------------------------------------------------- */
 const char* dinv_last_error(void);
-int dinv_version(void);   /* 12 = this header (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
+int dinv_version(void);   /* 13 = this header (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
 /* number of visible HIP devices (0 when no GPU): used by the host to fail loudly */
 int dinv_device_count(int* count);
 
@@ -639,6 +639,49 @@ int dinv_tgv_epsilon(int32_t nd, int64_t planes, int32_t D, int32_t H, int32_t W
  * (tgv.py:273-310; components on the first face of their axis are ignored).  out must not alias u. */
 int dinv_tgv_epsilon_adjoint(int32_t nd, int64_t planes, int32_t D, int32_t H, int32_t W, const float* u, float* out,
                              dinv_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
+/* Walsh-Hadamard transform and SinglePixelCamera (deepinv/physics/singlepixel.py:9-43, 292-439) */
+/* ------------------------------------------------------------------------- */
+/* fp32 only.  x and out are [P, H, W] contiguous and 16-byte aligned, H and W powers of two of at most
+ * DINV_HADAMARD_MAX_SIDE.  The transform is H2(x) = H_H x H_W / sqrt(H W) in natural (Sylvester) order, the order of the
+ * reference's hadamard_1d; it is symmetric and its own inverse.  The scale is applied once per 2-D transform (exact when H W
+ * is a power of four, the correctly rounded fp32 constant otherwise).  Planes of up to 2^14 floats (128 x 128) are transformed
+ * by one launch that holds them in LDS; larger ones by two launches (three for the operators with two transforms), the later
+ * ones in place on `out`.  x == out is allowed.  No atomics; the result is bit-reproducible.
+ * `ws` / `ws_bytes` are reserved (dinv_hadamard_workspace_bytes returns 0 for every shape today; null is accepted).
+ *
+ * dinv_hadamard: out = scale * H2(x).  flags: DINV_HAD_LAST_AXIS transforms the last axis only (hadamard_1d on [P H, W]),
+ * DINV_HAD_NO_NORMALIZE drops the 1 / sqrt factor (hadamard_1d(normalize=False)), DINV_HAD_RESIDENT_LOG2(c), c in 2..14, lowers
+ * the largest resident plane to 2^c floats (a test hook: it sends small planes through the two-pass form).
+ *
+ * dinv_hadamard_apply: every operator of SinglePixelCamera(fast=True) as ONE call,
+ *     out = scale * [H2] SYM( H2( PRE(x) ) )          ([H2]: with DINV_HAD_SECOND)
+ * over a real mask of mask_planes planes (plane p uses mask plane p % mask_planes: [1,C,H,W] shared by the batch or [B,C,H,W]):
+ *   DINV_HAD_PRE(1)  v <- mask v                          DINV_HAD_PRE(2)  v <- v (mask > 1e-5 ? 1 / mask : 0)
+ *   DINV_HAD_SYM(1)  v <- mask v                          DINV_HAD_SYM(2)  v <- mask^2 v
+ *   DINV_HAD_SYM(3)  v <- (mask y + add v) / (mask^2 + add)    (prox_l2: add = 1 / gamma; y null: y = 0)
+ *   DINV_HAD_SYM(4)  v <- mask v / (mask^2 + add)         DINV_HAD_SYM(5)  v <- v (mask > 1e-5 ? 1 / mask : 0)
+ *   DINV_HAD_NO_TRANSFORM: no transform at all, out = scale * SYM(x)  (A_A_adjoint: H2 H2 = I)
+ *     A x            SYM(1)                       A_adjoint y    PRE(1)
+ *     A_adjoint_A x  SYM(2) | SECOND              A_A_adjoint y  SYM(2) | NO_TRANSFORM
+ *     prox_l2        SYM(3) | SECOND, x = z       A_dagger y     PRE(2)
+ *   and their transposes for backward passes: SYM(4) is d prox / d y, SYM(5) the transpose of A_dagger.
+ * y must not alias out.  H W >= 4. */
+#define DINV_HADAMARD_MAX_SIDE 1024
+#define DINV_HAD_PRE(mode) (mode)
+#define DINV_HAD_SYM(mode) ((mode) << 4)
+#define DINV_HAD_SECOND 0x100
+#define DINV_HAD_NO_TRANSFORM 0x200
+#define DINV_HAD_LAST_AXIS 0x400
+#define DINV_HAD_NO_NORMALIZE 0x800
+#define DINV_HAD_RESIDENT_LOG2(c) ((c) << 16)
+size_t dinv_hadamard_workspace_bytes(int64_t P, int32_t H, int32_t W);
+int dinv_hadamard(const float* x, float* out, int64_t P, int32_t H, int32_t W, int32_t flags, float scale, void* ws,
+                  size_t ws_bytes, dinv_stream_t stream);
+int dinv_hadamard_apply(const float* x, const float* y, const float* mask, float* out, int64_t P, int32_t H, int32_t W,
+                        int64_t mask_planes, int32_t flags, float add, float scale, void* ws, size_t ws_bytes,
+                        dinv_stream_t stream);
 
 #ifdef __cplusplus
 }
