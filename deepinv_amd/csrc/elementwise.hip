@@ -1,5 +1,5 @@
 // Loop algebra of the iteration drivers as hand-written kernels (gfx950): the PGD gradient step, the CG vector
-// updates and the per-sample dot products.
+// updates, the per-sample dot products, and the pointwise gradients / proximal operators of the non-Gaussian likelihoods.
 //
 // Replaces the ATen elementwise / reduction launches behind
 //   fStepPGD.forward + L2.grad        deepinv/optim/optim_iterators/pgd.py:137-139, optim/data_fidelity.py:335-338
@@ -151,6 +151,38 @@ __global__ __launch_bounds__(256) void mask_solve_kernel(int mode, int64_t n, in
     }
 }
 
+// Pointwise gradients and proximal operators of the non-Gaussian distances (distance.py:196-263, 266-323, 372-395): one launch where
+// the reference's tensor expressions take four to seven.  The operations follow the reference's order (same divisions, same square root).
+__global__ __launch_bounds__(256) void fidelity_pointwise_kernel(int op, int64_t n, const float* __restrict__ x,
+                                                                 const float* __restrict__ y, float p0, float p1, float gamma,
+                                                                 int denorm, float* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float xv = x[i], yv = y[i];
+        const float yd = denorm ? yv / p0 : yv;
+        float r;
+        switch (op) {
+            case DINV_FID_POISSON_GRAD: r = p0 * (1.0f - yd / (xv / p0 + p1)); break;
+            case DINV_FID_POISSON_PROX: {
+                const float c = 1.0f / (p0 * gamma), d = xv - c;
+                r = (xv - c * sqrtf(d * d + 4.0f * yd / gamma)) / 2.0f;
+                break;
+            }
+            case DINV_FID_L1_GRAD: {
+                const float d = xv - yv;
+                r = d != d ? d : (float)((d > 0.f) - (d < 0.f));
+                break;
+            }
+            case DINV_FID_L1_PROX: {
+                const float d = xv - yv;     // softshrink passes a NaN through
+                r = (d > gamma ? d - gamma : d < -gamma ? d + gamma : d != d ? d : 0.f) + yv;
+                break;
+            }
+            default: r = p0 * p1 * (expf(-p1 * yv) - expf(-p1 * xv)); break;
+        }
+        out[i] = r;
+    }
+}
+
 inline unsigned stream_blocks(int64_t n) { return (unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div(n / 4 + 1, 256), 1), 2048); }
 
 }  // namespace
@@ -195,6 +227,17 @@ extern "C" int dinv_mask_solve(int32_t mode, int64_t n, int64_t period, const fl
     if (n == 0) return 0;
     hipLaunchKernelGGL(mask_solve_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 2048)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), mode, n, period, x, m, add, out);
+    DINV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dinv_fidelity_pointwise(int32_t op, int64_t n, const float* x, const float* y, float p0, float p1, float gamma,
+                                       int32_t flags, float* out, dinv_stream_t stream) {
+    DINV_REQUIRE(op >= DINV_FID_POISSON_GRAD && op <= DINV_FID_LOGPOISSON_GRAD, "unknown operation %d", op);
+    DINV_REQUIRE(n >= 0 && x && y && out && (flags & ~DINV_FID_DENORMALIZE) == 0, "bad arguments");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(fidelity_pointwise_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 2048)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), op, n, x, y, p0, p1, gamma, flags & DINV_FID_DENORMALIZE, out);
     DINV_CHECK_LAUNCH();
     return 0;
 }

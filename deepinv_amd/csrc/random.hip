@@ -1,7 +1,9 @@
-// Measurement synthesis on the device: additive Gaussian noise and the Cartesian MRI mask generators.
+// Measurement synthesis on the device: additive Gaussian noise, the Poisson-family noise models and the Cartesian MRI
+// mask generators.
 //
 // Reference semantics:
 //   GaussianNoise.forward           deepinv/physics/noise.py:197-330       y = x + sigma_b * N(0, 1)
+//   PoissonNoise / PoissonGaussianNoise / LogPoissonNoise   noise.py:417-505, 548-650, 704-769   (poisson_noise_kernel below)
 //   Random / GaussianMaskGenerator  deepinv/physics/generator/mri.py:134-196, 262-301
 //       per (batch, time) row: n_lines columns drawn WITHOUT replacement with probabilities pdf (zero on the centre
 //       band), the centre band always sampled, every image row gets the same columns
@@ -10,7 +12,7 @@
 //       (the polynomial variable density shifted by bisection to the target rate; centre band probability 1)
 //
 // The reference draws from torch's generators with a Python loop per sample; here one launch serves the whole batch.
-// Random numbers come from Philox4x32-10 (counter based: element i of a call uses counter (offset + i / 4), key = seed),
+// Random numbers come from Philox4x32-10 (counter based: element i of a Gaussian call uses counter (offset + i / 4), of a Poisson call counter (offset + i); key = seed),
 // so a call is reproducible from (seed, offset) and independent of the launch geometry.  The VALUES differ from torch's
 // stream (another use of the same generator family), the DISTRIBUTIONS are the reference's: sampling n columns without
 // replacement from pdf is done as "Gumbel top-n" (keys log p_w + G_w with G_w standard Gumbel; the n largest keys are
@@ -18,15 +20,18 @@
 // torch.multinomial(replacement=False) also implements).
 #include "common.hpp"
 
+#include <algorithm>
+#include <cmath>
+
 using namespace dinv;
 
 namespace {
 
 struct Philox {
     uint32_t c[4], k[2];
-    __device__ __forceinline__ Philox(uint64_t seed, uint64_t ctr, uint32_t stream) {
+    __device__ __forceinline__ Philox(uint64_t seed, uint64_t ctr, uint32_t stream, uint32_t round = 0u) {
         k[0] = (uint32_t)seed; k[1] = (uint32_t)(seed >> 32);
-        c[0] = (uint32_t)ctr; c[1] = (uint32_t)(ctr >> 32); c[2] = stream; c[3] = 0;
+        c[0] = (uint32_t)ctr; c[1] = (uint32_t)(ctr >> 32); c[2] = stream; c[3] = round;
     }
     __device__ __forceinline__ void round_() {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
@@ -69,6 +74,134 @@ __global__ __launch_bounds__(256) void gaussian_noise_kernel(int64_t n, int64_t 
                 const float s = sigma ? sigma[i / per_sample] : sigma_scalar;
                 y[i] = fmaf(s, z[e], x ? x[i] : 0.f);
             }
+        }
+    }
+}
+
+// ---- Poisson family (noise.py:417-505 PoissonNoise, 548-650 PoissonGaussianNoise, 704-769 LogPoissonNoise)
+//
+// Element i owns Philox counter (offset + i); the round of its sampling loop is the fourth counter word, so a call consumes n counters
+// however many rounds any element took.  Stream 4: the Poisson draw; stream 5: the Gaussian term of the Poisson-Gaussian mode.
+//
+// The sampler is exact at every rate (no normal approximation):
+//   lambda == 0          k = 0
+//   lambda <  10         multiplication: k = number of uniforms whose running product stays above exp(-lambda); four uniforms per round
+//   lambda >= 10         Hoermann's PTRS (transformed rejection with squeeze, Insurance: Mathematics and Economics 12 (1993) 39-45), in fp64.
+//                        Its acceptance test compares with log pmf(k) = -lambda + k log(lambda) - lgamma(k + 1), which cancels in fp32
+//                        from lambda ~ 1e4 on.  Here it is the algebraically equal  k log(lambda / k) + (k - lambda) - log sqrt(2 pi k)
+//                        - stirling(k)  (terms of size |k - lambda| and smaller instead of k log k), with the Stirling series to k^-7
+//                        (first dropped term 1 / (1188 k^9) <= 8.5e-13 at k = 10) and exact log k! below k = 10.
+// Both loops are bounded (POISSON_MAX_ROUNDS; DESIGN.md 3.11 derives it): a lane that reaches the bound returns what it has - the count
+// so far (small rates), floor(lambda) (PTRS) - instead of spinning.
+constexpr int POISSON_MAX_ROUNDS = 64;
+constexpr float POISSON_PTRS_FROM = 10.0f;
+
+__device__ __forceinline__ double log_factorial_small(int k) {   // log k!, k = 0..9
+    switch (k) {
+        case 0: case 1: return 0.0;
+        case 2: return 0.69314718055994530942;
+        case 3: return 1.79175946922805500081;
+        case 4: return 3.17805383034794561965;
+        case 5: return 4.78749174278204599425;
+        case 6: return 6.57925121201010099506;
+        case 7: return 8.52516136106541430017;
+        case 8: return 10.60460290274525022842;
+        default: return 12.80182748008146961121;
+    }
+}
+
+// log pmf(k; lam) for lam >= 10, k >= 0, in fp64
+__device__ __forceinline__ double poisson_log_pmf(double k, double lam) {
+    if (k < 10.0) return -lam + k * log(lam) - log_factorial_small((int)k);
+    const double r = 1.0 / k, r2 = r * r;
+    const double stirling = r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0 - r2 * (1.0 / 1680.0))));
+    return k * log(lam / k) + (k - lam) - 0.5 * log(6.28318530717958647692 * k) - stirling;
+}
+
+// one Poisson(lam) variate for a finite lam > 0 as a double holding an integer
+__device__ __forceinline__ double poisson_draw(float lam, uint64_t seed, uint64_t ctr) {
+    if (lam < POISSON_PTRS_FROM) {
+        const float limit = expf(-lam);
+        float prod = 1.0f;
+        int k = 0;
+        for (int round = 0; round < POISSON_MAX_ROUNDS; ++round) {
+            Philox ph(seed, ctr, 4u, (uint32_t)round);
+            ph.run();
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                prod *= u01(ph.c[e]);
+                if (!(prod > limit)) return (double)k;
+                ++k;
+            }
+        }
+        return (double)k;
+    }
+    const double l = (double)lam;
+    const double slam = sqrt(l);
+    const double b = 0.931 + 2.53 * slam;
+    const double a = -0.059 + 0.02483 * b;
+    const double inv_alpha = 1.1239 + 1.1328 / (b - 3.4);
+    const double vr = 0.9277 - 3.6224 / (b - 2.0);
+    for (int round = 0; round < POISSON_MAX_ROUNDS; ++round) {
+        Philox ph(seed, ctr, 4u, (uint32_t)round);
+        ph.run();
+        const double U = ((double)ph.c[0] + 0.5) * 2.3283064365386963e-10 - 0.5;      // (-0.5, 0.5), 32 bits
+        const double V = ((double)ph.c[1] + 0.5) * 2.3283064365386963e-10;            // (0, 1)
+        const double us = 0.5 - fabs(U);
+        const double k = floor((2.0 * a / us + b) * U + l + 0.43);
+        if (us >= 0.07 && V <= vr) return k;
+        if (k < 0.0 || (us < 0.013 && V > us)) continue;
+        if (log(V * inv_alpha / (a / (us * us) + b)) <= poisson_log_pmf(k, l)) return k;
+    }
+    return floor(l);
+}
+
+struct PoissonArgs {
+    int64_t per;         // elements per sample
+    int32_t batch;
+    int32_t mode, flags;
+    float gain, sigma, min_gain;   // scalars used where the tables are null
+    uint64_t seed, offset;
+};
+
+__global__ __launch_bounds__(256) void poisson_noise_kernel(PoissonArgs a, const float* __restrict__ x, const float* __restrict__ gain,
+                                                            const float* __restrict__ sigma, int32_t* __restrict__ bad,
+                                                            float* __restrict__ y) {
+    const bool clip = a.flags & DINV_POISSON_CLIP_POSITIVE;
+    for (int b = blockIdx.y; b < a.batch; b += gridDim.y) {
+        float g = gain ? gain[b] : a.gain;          // log-Poisson: N0
+        const float s = sigma ? sigma[b] : a.sigma; // log-Poisson: mu
+        if (a.mode == DINV_POISSON_GAUSSIAN) g = g != g ? g : fmaxf(g, a.min_gain);     // torch.clip keeps a NaN
+        if (bad && a.mode != DINV_POISSON_LOG && !(g > 0.f) && threadIdx.x == 0 && blockIdx.x == 0) bad[1] = 1;
+        for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < a.per; j += (int64_t)gridDim.x * 256) {
+            const int64_t i = (int64_t)b * a.per + j;
+            const float v = x[i];
+            float lam;
+            if (a.mode == DINV_POISSON_LOG) {
+                lam = g * expf(-v * s);
+            } else {
+                lam = v / g;
+                if (clip) lam = lam != lam ? lam : fmaxf(lam, 0.f);
+                else if (bad && v < 0.f) bad[0] = 1;
+            }
+            // only a finite, positive rate enters a sampling loop
+            float k;
+            if (lam != lam || lam < 0.f) k = __builtin_nanf("");
+            else if (lam == 0.f || lam == INFINITY) k = lam;
+            else k = (float)poisson_draw(lam, a.seed, a.offset + (uint64_t)i);
+            float out;
+            if (a.mode == DINV_POISSON_LOG) {
+                out = -logf(k / g) / s;
+            } else if (a.mode == DINV_POISSON_GAUSSIAN) {
+                Philox ph(a.seed, a.offset + (uint64_t)i, 5u);
+                ph.run();
+                float n0, n1;
+                box_muller(ph.c[0], ph.c[1], n0, n1);
+                out = k * g + n0 * s;
+            } else {
+                out = (a.flags & DINV_POISSON_NORMALIZE) ? k * g : k;
+            }
+            y[i] = out;
         }
     }
 }
@@ -152,6 +285,23 @@ extern "C" int dinv_gaussian_noise(int64_t n, int64_t per_sample, const float* x
     const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(nq, 256), 8192);
     hipLaunchKernelGGL(gaussian_noise_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), n, per_sample,
                        x, sigma_dev, sigma_scalar, seed, offset, y);
+    DINV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dinv_poisson_noise(int64_t n, int64_t per_sample, const float* x, const float* gain_dev, float gain_scalar,
+                                  const float* sigma_dev, float sigma_scalar, int32_t mode, int32_t flags, float min_gain,
+                                  uint64_t seed, uint64_t offset, int32_t* bad, float* y, dinv_stream_t stream) {
+    DINV_REQUIRE(n >= 0 && x && y && per_sample >= 1 && n % per_sample == 0, "bad arguments");
+    DINV_REQUIRE(mode >= DINV_POISSON && mode <= DINV_POISSON_LOG, "mode must be DINV_POISSON, DINV_POISSON_GAUSSIAN or DINV_POISSON_LOG");
+    DINV_REQUIRE((flags & ~(DINV_POISSON_NORMALIZE | DINV_POISSON_CLIP_POSITIVE)) == 0, "unknown flags 0x%x", flags);
+    DINV_REQUIRE(n / per_sample <= INT32_MAX, "too many samples");
+    if (n == 0) return 0;
+    PoissonArgs a{per_sample, (int32_t)(n / per_sample), mode, flags, gain_scalar, sigma_scalar, min_gain, seed, offset};
+    const unsigned by = (unsigned)std::min<int64_t>(a.batch, 65535);
+    const unsigned bx = (unsigned)std::max<int64_t>(std::min<int64_t>(ceil_div(per_sample, 256), 16384 / by), 1);
+    hipLaunchKernelGGL(poisson_noise_kernel, dim3(bx, by), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, x, gain_dev,
+                       sigma_dev, bad, y);
     DINV_CHECK_LAUNCH();
     return 0;
 }

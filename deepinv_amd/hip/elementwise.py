@@ -27,6 +27,7 @@ def _l():
         l.dinv_cg_check.argtypes = [i32, vp, vp, vp, vp]
         l.dinv_cdiv_real.argtypes = [i64, i64, vp, vp, f32, vp, vp]
         l.dinv_mask_solve.argtypes = [i32, i64, i64, vp, vp, f32, vp, vp]
+        l.dinv_fidelity_pointwise.argtypes = [i32, i64, vp, vp, f32, f32, f32, i32, vp, vp]
         _declared = True
     return l
 
@@ -129,3 +130,25 @@ def cg_update_p(num, den, eps, p, r, done=None):
 def cg_check(res, tol2, done):
     """done |= all(res < tol2), on the device (no host round trip)"""
     check(_l().dinv_cg_check(res.shape[0], ptr(res), ptr(tol2), ptr(done), stream_ptr(res.device)))
+
+
+FID_POISSON_GRAD, FID_POISSON_PROX, FID_L1_GRAD, FID_L1_PROX, FID_LOGPOISSON_GRAD = range(5)     # include/deepinv_amd.h: DINV_FID_*
+
+
+def fidelity_eligible(x, y, *scalars) -> bool:
+    """the pointwise kernel serves plain fp32 device tensors of one shape outside autograd, with Python-number parameters"""
+    if not (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and x.is_cuda and y.is_cuda and x.shape == y.shape
+            and x.dtype == torch.float32 and y.dtype == torch.float32):
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+        return False
+    return all(isinstance(s, (int, float)) for s in scalars)
+
+
+def fidelity_pointwise(op: int, x, y, p0: float = 1.0, p1: float = 0.0, gamma: float = 1.0, denormalize: bool = False):
+    """grad / prox of the Poisson, L1 and log-Poisson distances in one launch (dinv_fidelity_pointwise, csrc/elementwise.hip)"""
+    xc, yc = x.contiguous(), y.contiguous()
+    out = torch.empty_like(xc)
+    check(_l().dinv_fidelity_pointwise(int(op), xc.numel(), ptr(xc), ptr(yc), float(p0), float(p1), float(gamma),
+                                       1 if denormalize else 0, ptr(out), stream_ptr(xc.device)))
+    return out

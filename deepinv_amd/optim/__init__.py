@@ -1,6 +1,6 @@
 from .potential import Potential
-from .distance import Distance, L2Distance
-from .data_fidelity import DataFidelity, L2, ZeroFidelity
+from .distance import Distance, L2Distance, PoissonLikelihoodDistance, L1Distance, LogPoissonLikelihoodDistance
+from .data_fidelity import DataFidelity, L2, ZeroFidelity, PoissonLikelihood, L1, LogPoissonLikelihood
 from .prior import Prior, PnP, ZeroPrior, TVPrior, TVL1Prior
 from .optim_iterators import (OptimIterator, fStep, gStep, PGDIteration, HQSIteration)
 from .fixed_point import FixedPoint

@@ -1,10 +1,10 @@
-"""Data-fidelity terms (reference deepinv/optim/data_fidelity.py:26-338)."""
+"""Data-fidelity terms (reference deepinv/optim/data_fidelity.py:26-338, 663-795)."""
 from __future__ import annotations
 
 import torch
 
 from ..physics.forward import LinearPhysics
-from .distance import Distance, L2Distance
+from .distance import Distance, L1Distance, L2Distance, LogPoissonLikelihoodDistance, PoissonLikelihoodDistance
 from .potential import Potential
 
 
@@ -57,3 +57,48 @@ class L2(DataFidelity):
         if isinstance(physics, LinearPhysics):
             return self.norm * (physics.A_adjoint_A(x) - physics.A_adjoint(y))
         return super().grad(x, y, physics, *args, **kwargs)
+
+
+class PoissonLikelihood(DataFidelity):
+    r""":math:`-y^\top\log(z+\beta) + 1^\top z` (data_fidelity.py:663-689); ``denormalize`` defaults to True here, to False in
+    the distance, as in the reference."""
+
+    def __init__(self, gain=1.0, bkg=0, denormalize: bool = True):
+        super().__init__()
+        self.d = PoissonLikelihoodDistance(gain=gain, bkg=bkg, denormalize=denormalize)
+        self.bkg = bkg
+        self.gain = gain
+        self.normalize = denormalize
+
+
+class L1(DataFidelity):
+    r""":math:`\|Ax-y\|_1` (data_fidelity.py:692-754)."""
+
+    def __init__(self):
+        super().__init__()
+        self.d = L1Distance()
+
+    def prox(self, x, y, physics, *args, gamma=1.0, stepsize=None, crit_conv=1e-5, max_iter=100, **kwargs):
+        """dual forward-backward iterations (no closed form for a general operator)"""
+        norm_AtA = physics.compute_sqnorm(x)
+        stepsize = 1.0 / norm_AtA if stepsize is None else stepsize
+        u = x.clone()
+        for it in range(max_iter):
+            u_prev = u.clone()
+            t = x - physics.A_adjoint(u)
+            u_ = u + stepsize * physics.A(t)
+            u = u_ - stepsize * self.d.prox(u_ / stepsize, y, gamma / stepsize)
+            rel_crit = ((u - u_prev).norm()) / (u.norm() + 1e-12)
+            if rel_crit < crit_conv and it > 2:
+                break
+        return t
+
+
+class LogPoissonLikelihood(DataFidelity):
+    r""":math:`N_0(1^\top e^{-\mu z} + \mu\, (e^{-\mu y})^\top z)` (data_fidelity.py:776-795); pairs with ``LogPoissonNoise``."""
+
+    def __init__(self, N0=1024.0, mu=1 / 50.0):
+        super().__init__()
+        self.d = LogPoissonLikelihoodDistance(N0=N0, mu=mu)
+        self.mu = mu
+        self.N0 = N0

@@ -35,7 +35,7 @@ typedef void* dinv_stream_t; /* hipStream_t */
 /* library / error                                                            */
 /* ------------------------------------------------------------------------- */
 const char* dinv_last_error(void);
-int dinv_version(void);   /* 13 = this header (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
+int dinv_version(void);   /* 14 = this header (adds dinv_poisson_noise and dinv_fidelity_pointwise); 13: (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
 /* number of visible HIP devices (0 when no GPU): used by the host to fail loudly */
 int dinv_device_count(int* count);
 
@@ -412,15 +412,35 @@ int dinv_radon_ramp_fft(int32_t n_img, int32_t n_det, int32_t n_angles, int32_t 
                         dinv_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
-/* Measurement synthesis on the device: additive Gaussian noise                */
+/* Measurement synthesis on the device: additive Gaussian noise, Poisson noise */
 /* (deepinv/physics/noise.py:197-330) and Cartesian MRI acceleration masks     */
 /* (deepinv/physics/generator/mri.py:15-384).  Philox4x32-10: element i of a   */
-/* call uses counter offset + i/4 under key `seed`.                            */
+/* Gaussian call uses counter offset + i/4 under key `seed` (Poisson: offset + i). */
 /* ------------------------------------------------------------------------- */
 /* y[i] = x[i] + sigma * N(0,1); sigma = sigma_dev[i / per_sample] when sigma_dev != NULL, else sigma_scalar;
  * x may be NULL (pure noise). */
 int dinv_gaussian_noise(int64_t n, int64_t per_sample, const float* x, const float* sigma_dev, float sigma_scalar,
                         uint64_t seed, uint64_t offset, float* y, dinv_stream_t stream);
+/* Poisson-family noise in one pass over n floats (deepinv/physics/noise.py:417-505 PoissonNoise, 548-650 PoissonGaussianNoise,
+ * 704-769 LogPoissonNoise).  gain and sigma are read like the sigma of dinv_gaussian_noise: gain_dev[i / per_sample] when gain_dev !=
+ * NULL, else gain_scalar (per_sample must divide n).  k ~ Poisson(lambda_i) is exact at every rate (multiplication below lambda = 10,
+ * Hoermann's PTRS with an fp64 acceptance test from there on), with both loops bounded by 64 rounds.
+ *   DINV_POISSON           lambda = x / gain (clamped at 0 under DINV_POISSON_CLIP_POSITIVE);  y = k, or gain k under DINV_POISSON_NORMALIZE
+ *   DINV_POISSON_GAUSSIAN  g = max(gain, min_gain); lambda = x / g (clamped likewise);         y = g k + sigma N(0, 1)
+ *   DINV_POISSON_LOG       gain carries N0 and sigma carries mu: lambda = N0 exp(-mu x);        y = -log(k / N0) / mu  (k = 0: +inf)
+ * lambda = 0 gives k = 0, lambda = +inf gives k = +inf, a NaN or negative lambda gives NaN; none of them enters a sampling loop.
+ * Element i draws from Philox counter offset + i under key `seed` (streams 4 and 5; the round of the sampling loop is the fourth counter
+ * word), so a call consumes n counters and its result does not depend on the launch geometry.
+ * `bad` (two int32 on the device, zeroed by the caller; may be NULL; unused by DINV_POISSON_LOG): without DINV_POISSON_CLIP_POSITIVE
+ * the kernel sets bad[0] when some x < 0 and bad[1] when some gain is not positive - the two conditions the reference raises on. */
+#define DINV_POISSON 0
+#define DINV_POISSON_GAUSSIAN 1
+#define DINV_POISSON_LOG 2
+#define DINV_POISSON_NORMALIZE 1
+#define DINV_POISSON_CLIP_POSITIVE 2
+int dinv_poisson_noise(int64_t n, int64_t per_sample, const float* x, const float* gain_dev, float gain_scalar,
+                       const float* sigma_dev, float sigma_scalar, int32_t mode, int32_t flags, float min_gain, uint64_t seed,
+                       uint64_t offset, int32_t* bad, float* y, dinv_stream_t stream);
 /* mask[batch, channels, times, height, width] of k-space columns.  mode 0: per (batch, time) row, n_lines columns
  * without replacement with probabilities pdf_dev[width] (zero on the centre band [center_lo, center_hi), which is
  * always sampled); mode 1: equispaced columns round(arange((t + offset_b) % accel, width - 1, accel)) with
@@ -535,6 +555,22 @@ int dinv_cg_update_masked(int32_t mode, int32_t batch, int64_t n, const float* n
                           float* v0, float* v1, const float* w0, const float* w1, const int32_t* done,
                           dinv_stream_t stream);
 int dinv_cg_check(int32_t batch, const float* res, const float* tol2, int32_t* done, dinv_stream_t stream);
+/* The pointwise gradients and proximal operators of the non-Gaussian distances in one launch each (deepinv/optim/distance.py:196-263
+ * PoissonLikelihoodDistance, 266-323 L1Distance, 372-395 LogPoissonLikelihoodDistance); n floats, any alignment, x and out may alias.
+ * With yd = y / p0 under DINV_FID_DENORMALIZE and yd = y otherwise:
+ *   DINV_FID_POISSON_GRAD     out = p0 (1 - yd / (x / p0 + p1))                                   p0 = gain, p1 = bkg
+ *   DINV_FID_POISSON_PROX     out = (x - c sqrt((x - c)^2 + 4 yd / gamma)) / 2,  c = 1 / (p0 gamma)  p0 = gain
+ *   DINV_FID_L1_GRAD          out = sign(x - y)
+ *   DINV_FID_L1_PROX          out = y + softshrink(x - y, gamma)
+ *   DINV_FID_LOGPOISSON_GRAD  out = p0 p1 (exp(-p1 y) - exp(-p1 x))                               p0 = N0, p1 = mu */
+#define DINV_FID_POISSON_GRAD 0
+#define DINV_FID_POISSON_PROX 1
+#define DINV_FID_L1_GRAD 2
+#define DINV_FID_L1_PROX 3
+#define DINV_FID_LOGPOISSON_GRAD 4
+#define DINV_FID_DENORMALIZE 1
+int dinv_fidelity_pointwise(int32_t op, int64_t n, const float* x, const float* y, float p0, float p1, float gamma, int32_t flags,
+                            float* out, dinv_stream_t stream);
 /* out[i] = s[i] / (d[i mod period] + add) for n interleaved complex values s over a real symbol d of `period` entries shared by the
  * leading (batch, channel) dimensions: the pointwise division of the closed-form proxes - Downsampling.prox_l2
  * (deepinv/physics/blur.py:331-363: mean_blocks(|K|^2) + 1/gamma) and DecomposablePhysics.prox_l2 with a real singular-value
