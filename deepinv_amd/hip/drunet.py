@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import torch
 
@@ -128,16 +129,23 @@ def pack_bias(b: torch.Tensor | None, cout_p: int, device=None) -> torch.Tensor:
     return out
 
 
+def _bf16_parts(w: torch.Tensor, n: int) -> list[torch.Tensor]:
+    """the exact n-part bf16 split of an fp32 tensor, leading part first: every part is the residual left by the parts before it,
+    rounded to nearest even (n = 2: hi = bf16(w), lo = bf16(w - hi); n = 3: hi, mid, lo - 24 significand bits)"""
+    parts = [w.bfloat16()]
+    for _ in range(n - 1):
+        w = w - parts[-1].float()
+        parts.append(w.bfloat16())
+    return parts
+
+
 def _pack_split_weight(w: torch.Tensor) -> torch.Tensor:
     """OIHW [Cout,Cin,3,3] -> two-part bf16 split (hi = bf16(w), lo = bf16(w - hi)),
     [Cout/64][Cin/16][dy 3][plane 2][dx 3][cblk 2][co 64][ci 8] (bf16)"""
     cout, cin = w.shape[:2]
     if cin % 16 or cout % 64:
         raise ValueError(f"bf16-split packing needs cin % 16 == 0 and cout % 64 == 0, got {cin},{cout}")
-    w = w.detach().float()
-    hi = w.bfloat16()
-    lo = (w - hi.float()).bfloat16()
-    planes = torch.stack((hi, lo))                                            # [2, Cout, Cin, 3, 3]
+    planes = torch.stack(_bf16_parts(w.detach().float(), 2))                  # [2, Cout, Cin, 3, 3]
     planes = planes.reshape(2, cout // 64, 64, cin // 16, 2, 8, 3, 3)         # pl, ct, co, s, cblk, ci, dy, dx
     return planes.permute(1, 3, 6, 0, 7, 4, 2, 5).contiguous()               # ct, s, dy, pl, dx, cblk, co, ci
 
@@ -171,9 +179,7 @@ def pack_wsplit_weight(w: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"Winograd bf16-split packing needs cin % 16 == 0 and cout % 64 == 0, got {cin},{cout}")
     g = w.detach().double()                                                     # [co, ci, dy, dx]
     u = torch.stack((g[..., 0], (g[..., 0] + g[..., 1] + g[..., 2]) / 2, (g[..., 0] - g[..., 1] + g[..., 2]) / 2, g[..., 2])).float()
-    hi = u.bfloat16()
-    lo = (u - hi.float()).bfloat16()
-    planes = torch.stack((hi, lo))                                               # [pl 2, k 4, co, ci, dy 3]
+    planes = torch.stack(_bf16_parts(u, 2))                                      # [pl 2, k 4, co, ci, dy 3]
     planes = planes.reshape(2, 4, cout // 64, 2, 32, cin // 16, 2, 8, 3)         # pl, k, ct, m, r, s, cblk, ci, dy
     planes = planes.index_select(4, split2d_row_perm().to(planes.device))
     return planes.permute(2, 5, 8, 1, 3, 0, 6, 4, 7).contiguous()               # ct, s, dy, k, m, pl, cblk, r, ci
@@ -252,10 +258,7 @@ def pack_winograd4_bf16x3_weight(w: torch.Tensor) -> torch.Tensor:
     point) 1536 bytes = [lane 64][um 4 | uh 4] then [lane 64][ul 4] (bf16): the (um, uh) and (uh, ul) operand windows of the
     wave's three bf16 MFMAs, loaded as 16 + 8 bytes per lane.  Returns a bfloat16 tensor [Cout/64][Cin/8][8][9][768]"""
     u = pack_winograd4_weight(w)                                        # ct, cb, c2, q, k, h, r, m   (fp32)
-    hi = u.bfloat16()
-    r1 = u - hi.float()
-    mid = r1.bfloat16()
-    lo = (r1 - mid.float()).bfloat16()
+    hi, mid, lo = _bf16_parts(u, 3)
     ct, cb = u.shape[:2]
     mh = torch.stack((mid, hi), dim=-2).reshape(ct, cb, 8, 9, 512)      # [h, r][part 2][m 4]
     return torch.cat((mh, lo.reshape(ct, cb, 8, 9, 256)), dim=-1).contiguous()
@@ -267,31 +270,19 @@ def pack_down_weight(w: torch.Tensor) -> torch.Tensor:
     return w.detach().float().permute(2, 3, 1, 0).reshape(4, cin // 8, 8, cout).permute(0, 1, 3, 2).contiguous()
 
 
-def pack_down_bf16s_weight(w: torch.Tensor) -> torch.Tensor:
-    """Conv2d k2 s2 weight [Cout,Cin,2,2] -> two-part bf16 split packed [tap=dy*2+dx][Cin/16][plane 2][cblk 2][Cout][ci 8]"""
+def pack_down_bf16s_weight(w: torch.Tensor, parts: int = 2) -> torch.Tensor:
+    """Conv2d k2 s2 weight [Cout,Cin,2,2] -> `parts`-part bf16 split packed [tap=dy*2+dx][Cin/16][plane `parts`][cblk 2][Cout][ci 8]"""
     cout, cin = w.shape[:2]
     if cin % 16 or cout % 64:
         raise ValueError(f"bf16-split down packing needs cin % 16 == 0 and cout % 64 == 0, got {cin},{cout}")
-    w = w.detach().float()
-    hi = w.bfloat16()
-    lo = (w - hi.float()).bfloat16()
-    planes = torch.stack((hi, lo)).reshape(2, cout, cin // 16, 2, 8, 2, 2)        # pl, co, s, cblk, ci, dy, dx
+    planes = torch.stack(_bf16_parts(w.detach().float(), parts)).reshape(parts, cout, cin // 16, 2, 8, 2, 2)   # pl, co, s, cblk, ci, dy, dx
     return planes.permute(5, 6, 2, 0, 3, 1, 4).contiguous()                       # dy, dx, s, pl, cblk, co, ci
 
 
 def pack_down_bf16x3_weight(w: torch.Tensor) -> torch.Tensor:
     """Conv2d k2 s2 weight [Cout,Cin,2,2] -> THREE-part bf16 split (hi, mid, lo: 24 significand bits) packed
     [tap=dy*2+dx][Cin/16][plane 3][cblk 2][Cout][ci 8] for dinv_conv_down2x2_bf16x3 (six products: fp32-equivalent)"""
-    cout, cin = w.shape[:2]
-    if cin % 16 or cout % 64:
-        raise ValueError(f"bf16x3 down packing needs cin % 16 == 0 and cout % 64 == 0, got {cin},{cout}")
-    w = w.detach().float()
-    hi = w.bfloat16()
-    r1 = w - hi.float()
-    mid = r1.bfloat16()
-    lo = (r1 - mid.float()).bfloat16()
-    planes = torch.stack((hi, mid, lo)).reshape(3, cout, cin // 16, 2, 8, 2, 2)   # pl, co, s, cblk, ci, dy, dx
-    return planes.permute(5, 6, 2, 0, 3, 1, 4).contiguous()                       # dy, dx, s, pl, cblk, co, ci
+    return pack_down_bf16s_weight(w, parts=3)
 
 
 def pack_up_bf16s_weight(w: torch.Tensor) -> torch.Tensor:
@@ -299,10 +290,7 @@ def pack_up_bf16s_weight(w: torch.Tensor) -> torch.Tensor:
     cin, cout = w.shape[:2]
     if cin % 16 or cout % 64:
         raise ValueError(f"bf16-split up packing needs cin % 16 == 0 and cout % 64 == 0, got {cin},{cout}")
-    w = w.detach().float()
-    hi = w.bfloat16()
-    lo = (w - hi.float()).bfloat16()
-    planes = torch.stack((hi, lo)).reshape(2, cin // 16, 2, 8, cout, 2, 2)        # pl, s, cblk, ci, co, dy, dx
+    planes = torch.stack(_bf16_parts(w.detach().float(), 2)).reshape(2, cin // 16, 2, 8, cout, 2, 2)   # pl, s, cblk, ci, co, dy, dx
     return planes.permute(1, 5, 6, 0, 2, 4, 3).contiguous()                       # s, dy, dx, pl, cblk, co, ci
 
 
@@ -310,6 +298,44 @@ def pack_up_weight(w: torch.Tensor) -> torch.Tensor:
     """ConvTranspose2d k2 s2 weight [Cin,Cout,2,2] -> [tap=dy*2+dx][Cin/8][Cout][8]"""
     cin, cout = w.shape[:2]
     return w.detach().float().permute(2, 3, 0, 1).reshape(4, cin // 8, 8, cout).permute(0, 1, 3, 2).contiguous()
+
+
+class ConvPacks(NamedTuple):
+    """the packs of ONE 3x3 convolution, one field per kernel that may run it (None: that kernel does not take the layer)"""
+    p64: torch.Tensor                       # direct fp32 kernel, 64-wide cout tiles (32-wide where cout_p % 64: then p32 is p64)
+    p32: torch.Tensor                       # direct fp32 kernel, 32-wide cout tiles
+    cin_p: int                              # padded channel counts of the two direct packs (what the launches are given)
+    cout_p: int
+    wino2: torch.Tensor | None = None       # pack_winograd_weight
+    split2d: torch.Tensor | None = None     # pack_split2d_weight
+    wsplit: torch.Tensor | None = None      # pack_wsplit_weight
+    wino4: torch.Tensor | None = None       # pack_winograd4_weight
+    wino4x3: torch.Tensor | None = None     # pack_winograd4_bf16x3_weight
+    bias: torch.Tensor | None = None        # pack_bias to cout_p
+
+    def pick(self, g) -> torch.Tensor:
+        """the direct pack for launch geometry g: 64-wide cout tiles unless that grid would leave the chip under-filled (< 3 rounds
+        of the 512 resident workgroup slots): then 32-wide tiles double the number of workgroups (small per-GPU batches)"""
+        if self.p64.shape[3] == 64 and ((g.np + 255) // 256) * (self.cout_p // 64) < 1536:
+            return self.p32
+        return self.p64
+
+
+def conv_packs(w: torch.Tensor, bias: torch.Tensor | None = None, precision: str | None = None) -> ConvPacks:
+    """ConvPacks of an OIHW weight: the two direct packs and the bias; with `precision`, also the packs of that setting's ResBlock
+    kernels where the layer has their shape ("bf16split": split2d, wsplit; "fp32": wino2, wino4 and, with FP32_WINOGRAD4_BF16X3,
+    wino4x3)"""
+    p64, cin_p, cout_p = pack_conv3x3_weight(w)
+    p32 = pack_conv3x3_weight(w, mt=32)[0] if p64.shape[3] == 64 else p64
+    ok = w.shape[0] % 64 == 0 and w.shape[1] % 16 == 0
+    split, fp32 = ok and precision == "bf16split", ok and precision == "fp32"
+    return ConvPacks(p64, p32, cin_p, cout_p,
+                     wino2=pack_winograd_weight(w) if fp32 and w.shape[1] >= 32 else None,
+                     split2d=pack_split2d_weight(w) if split else None,
+                     wsplit=pack_wsplit_weight(w) if split else None,
+                     wino4=pack_winograd4_weight(w) if fp32 else None,
+                     wino4x3=pack_winograd4_bf16x3_weight(w) if fp32 and FP32_WINOGRAD4_BF16X3 else None,
+                     bias=pack_bias(bias, cout_p) if bias is not None else None)
 
 
 # Packed weights of the training / 3-D paths are cached per source tensor: an unfolded network calls the denoiser
@@ -341,6 +367,13 @@ def cached_pack(kind, w, make, sub=0):
             _PACKS.clear()
         hit = _PACKS[key] = (make(), ver, w)
     return hit[0]
+
+
+def weights_version(module) -> tuple:
+    """changes whenever a parameter of `module` is updated in place or replaced: what the packs a model keeps were made from
+    (tensors created under torch.inference_mode() carry no version counter - reading it raises)"""
+    params = list(module.parameters())
+    return tuple(0 if p.is_inference() else p._version for p in params) + tuple(p.data_ptr() for p in params)
 
 
 def pack_input(g, x, sigma, act):
@@ -392,24 +425,38 @@ def profile_end():
     return out
 
 
+class _profiled:
+    """``with _profiled(kernel, direct_flops, mfma_flops):`` around ONE launch - between profile_begin() and profile_end() the launch
+    is bracketed by two HIP events and noted under the kernel's name with its two flop counts; otherwise nothing happens"""
+    __slots__ = ("rec",)
+
+    def __init__(self, kernel, direct_flops, mfma_flops):
+        self.rec = None
+        if _prof is not None:
+            self.rec = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), kernel, direct_flops, mfma_flops)
+
+    def __enter__(self):
+        if self.rec is not None:
+            self.rec[0].record()
+
+    def __exit__(self, *exc):
+        if self.rec is not None:
+            self.rec[1].record()
+            _prof.append(self.rec)
+
+
+def _conv_flops(g, cin, cout):
+    """2 * 9 * Cin * Cout per interior pixel: what the direct form of a 3x3 convolution executes"""
+    return 2.0 * 9 * cin * cout * g.batch * g.height * g.width
+
+
 def conv3x3(g, x, wpk, cin, cout, y, cout_valid=None, x2=None, res1=None, res2=None, relu=False, cin_valid=None):
     """wpk: packed weight tensor [cout/MT][cin/8][9][MT][8]; MT is read off its shape"""
-    if _prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _conv3x3(g, x, wpk, cin, cout, y, cout_valid, x2, res1, res2, relu)
-        e1.record()
-        co = cout if cout_valid is None else cout_valid
-        ci = cin if cin_valid is None else cin_valid
-        fl = 2.0 * 9 * ci * co * g.batch * g.height * g.width
-        _prof.append((e0, e1, "conv3x3_kernel", fl, fl))
-        return
-    _conv3x3(g, x, wpk, cin, cout, y, cout_valid, x2, res1, res2, relu)
-
-
-def _conv3x3(g, x, wpk, cin, cout, y, cout_valid=None, x2=None, res1=None, res2=None, relu=False):
-    check(_l().dinv_conv3x3(ctypes.byref(g), ptr(x), ptr(x2), ptr(wpk), cin, cout, cout if cout_valid is None else cout_valid,
-                            int(wpk.shape[3]), ptr(y), ptr(res1), ptr(res2), int(relu), stream_ptr(y.device)))
+    co = cout if cout_valid is None else cout_valid
+    fl = _conv_flops(g, cin if cin_valid is None else cin_valid, co)
+    with _profiled("conv3x3_kernel", fl, fl):
+        check(_l().dinv_conv3x3(ctypes.byref(g), ptr(x), ptr(x2), ptr(wpk), cin, cout, co, int(wpk.shape[3]), ptr(y), ptr(res1),
+                                ptr(res2), int(relu), stream_ptr(y.device)))
 
 
 def pack_conv3x3x3_weight(w5: torch.Tensor) -> tuple[torch.Tensor, int, int]:
@@ -446,30 +493,20 @@ def conv3x3_split(g, x, wsplit, cin, cout, y, res1=None, relu=False, x_presplit=
     """y = [relu](conv3x3(x)) (+res1) on the bf16 matrix cores, two-part exact operand split, 2-D pixel tiles
     (csrc/drunet_split2d.hip); wsplit from pack_split2d_weight.  `x_presplit` / `y_presplit`: the activation buffer holds
     (8 bf16 high parts | 8 bf16 low parts) per pixel and channel block instead of 8 fp32 values (same 32 bytes)."""
-    if _prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     flags = (1 if x_presplit else 0) | (2 if y_presplit else 0) | (4 if relu else 0) | (8 if gate else 0)   # gate: y = res1 > 0 ? conv : 0
-    check(_l().dinv_conv3x3_split(ctypes.byref(g), ptr(x), ptr(wsplit), cin, cout, ptr(y), ptr(res1), flags,
-                                  stream_ptr(y.device)))
-    if _prof is not None:
-        e1.record()
-        fl = 2.0 * 9 * cin * cout * g.batch * g.height * g.width
-        _prof.append((e0, e1, "conv3x3_split2d_kernel", fl, 3.0 * fl))
+    fl = _conv_flops(g, cin, cout)
+    with _profiled("conv3x3_split2d_kernel", fl, 3.0 * fl):
+        check(_l().dinv_conv3x3_split(ctypes.byref(g), ptr(x), ptr(wsplit), cin, cout, ptr(y), ptr(res1), flags,
+                                      stream_ptr(y.device)))
 
 
 def conv3x3_wsplit(g, x, wws, cin, cout, y, res1=None, relu=False):
     """y = [relu](conv3x3(x)) (+res1): Winograd F(2,3) along rows on the bf16 matrix cores, two-part operand split
     (csrc/drunet_wsplit.hip); wws from pack_wsplit_weight; even image width"""
-    if _prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_l().dinv_conv3x3_wsplit(ctypes.byref(g), ptr(x), ptr(wws), cin, cout, ptr(y), ptr(res1), 4 if relu else 0,
-                                   stream_ptr(y.device)))
-    if _prof is not None:
-        e1.record()
-        fl = 2.0 * 9 * cin * cout * g.batch * g.height * g.width
-        _prof.append((e0, e1, "conv3x3_wsplit_kernel", fl, 2.0 * fl))      # 12 of 18 multiplies, three products each
+    fl = _conv_flops(g, cin, cout)
+    with _profiled("conv3x3_wsplit_kernel", fl, 2.0 * fl):                 # 12 of 18 multiplies, three products each
+        check(_l().dinv_conv3x3_wsplit(ctypes.byref(g), ptr(x), ptr(wws), cin, cout, ptr(y), ptr(res1), 4 if relu else 0,
+                                       stream_ptr(y.device)))
 
 
 def conv3x3x3_split(g, x, wsplit, cin, cout, y, depth, res1=None, relu=False, x_presplit=False, y_presplit=False, gate=False):
@@ -483,16 +520,10 @@ def conv3x3x3_split(g, x, wsplit, cin, cout, y, depth, res1=None, relu=False, x_
 
 def conv3x3_winograd(g, x, wino, cin, cout, y, res1=None, relu=False):
     """y = [relu](conv3x3(x)) (+res1) via Winograd F(2x2,3x3); wino from pack_winograd_weight"""
-    if _prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_l().dinv_conv3x3_winograd(ctypes.byref(g), ptr(x), ptr(wino), cin, cout, ptr(y), ptr(res1), int(relu),
-                                     stream_ptr(y.device)))
-    if _prof is not None:
-        e1.record()
-        tiles = g.batch * ((g.height + 1) // 2) * ((g.width + 1) // 2)
-        _prof.append((e0, e1, "conv3x3_wino_kernel", 2.0 * 9 * cin * cout * g.batch * g.height * g.width,
-                      2.0 * 16 * cin * cout * tiles))
+    tiles = g.batch * ((g.height + 1) // 2) * ((g.width + 1) // 2)
+    with _profiled("conv3x3_wino_kernel", _conv_flops(g, cin, cout), 2.0 * 16 * cin * cout * tiles):
+        check(_l().dinv_conv3x3_winograd(ctypes.byref(g), ptr(x), ptr(wino), cin, cout, ptr(y), ptr(res1), int(relu),
+                                         stream_ptr(y.device)))
 
 
 _W4_WS: dict = {}
@@ -527,32 +558,20 @@ def winograd4_last_split():
 def conv3x3_winograd4(g, x, wino4, cin, cout, y, res1=None, relu=False, workspace=None):
     """y = [relu](conv3x3(x)) (+res1) via Winograd F(4x4,3x3) on the fp32 matrix cores (csrc/drunet_wino4.hip); wino4 from
     pack_winograd4_weight; height and width multiples of 4; `workspace` (winograd4_workspace(device)) enables the tail split"""
-    if _prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_l().dinv_conv3x3_winograd4(ctypes.byref(g), ptr(x), ptr(wino4), cin, cout, ptr(y), ptr(res1), int(relu),
-                                      ptr(workspace), 0 if workspace is None else workspace.numel(), stream_ptr(y.device)))
-    if _prof is not None:
-        e1.record()
-        tiles = g.batch * (g.height // 4) * (g.width // 4)
-        _prof.append((e0, e1, "conv3x3_wino4_kernel", 2.0 * 9 * cin * cout * g.batch * g.height * g.width,
-                      2.0 * 36 * cin * cout * tiles))
+    tiles = g.batch * (g.height // 4) * (g.width // 4)
+    with _profiled("conv3x3_wino4_kernel", _conv_flops(g, cin, cout), 2.0 * 36 * cin * cout * tiles):
+        check(_l().dinv_conv3x3_winograd4(ctypes.byref(g), ptr(x), ptr(wino4), cin, cout, ptr(y), ptr(res1), int(relu),
+                                          ptr(workspace), 0 if workspace is None else workspace.numel(), stream_ptr(y.device)))
 
 
 def conv3x3_winograd4_bf16x3(g, x, wino4x3, cin, cout, y, res1=None, relu=False, workspace=None):
     """conv3x3_winograd4 with the multiplies as a three-part bf16 split, six products on the bf16 matrix cores (fp32-equivalent:
     csrc/drunet_wino4.hip, BF3); wino4x3 from pack_winograd4_bf16x3_weight"""
-    if _prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_l().dinv_conv3x3_winograd4_bf16x3(ctypes.byref(g), ptr(x), ptr(wino4x3), cin, cout, ptr(y), ptr(res1), int(relu),
-                                             ptr(workspace), 0 if workspace is None else workspace.numel(), stream_ptr(y.device)))
-    if _prof is not None:
-        e1.record()
-        tiles = g.batch * (g.height // 4) * (g.width // 4)
-        # executed: 6 bf16 products per fp32 multiply of the F(4x4) form
-        _prof.append((e0, e1, "conv3x3_wino4_kernel<bf16x3>", 2.0 * 9 * cin * cout * g.batch * g.height * g.width,
-                      2.0 * 6 * 36 * cin * cout * tiles))
+    tiles = g.batch * (g.height // 4) * (g.width // 4)
+    # executed: 6 bf16 products per fp32 multiply of the F(4x4) form
+    with _profiled("conv3x3_wino4_kernel<bf16x3>", _conv_flops(g, cin, cout), 2.0 * 6 * 36 * cin * cout * tiles):
+        check(_l().dinv_conv3x3_winograd4_bf16x3(ctypes.byref(g), ptr(x), ptr(wino4x3), cin, cout, ptr(y), ptr(res1), int(relu),
+                                                 ptr(workspace), 0 if workspace is None else workspace.numel(), stream_ptr(y.device)))
 
 
 def down2x2(gi, go, x, w, cin, cout, y):
@@ -637,42 +656,25 @@ def conv3x3_bias(g, x, wpk, bias, cin, cout, y, cout_valid=None, res1=None, relu
     """y = relu(conv3x3(x) + bias) or conv3x3(x) + bias (+res1) on the direct fp32 kernel; wpk from pack_conv3x3_weight (MT = 32 / 64)
     or pack_thin_weight (cout = 16); bias from pack_bias (cout floats)"""
     mt = int(wpk.shape[3])
-    if _prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_l().dinv_conv3x3_bias(ctypes.byref(g), ptr(x), ptr(wpk), ptr(bias), cin, cout, cout if cout_valid is None else cout_valid,
-                                 mt, ptr(y), ptr(res1), int(relu), stream_ptr(y.device)))
-    if _prof is not None:
-        e1.record()
-        fl = 2.0 * 9 * cin * (cout if cout_valid is None else cout_valid) * g.batch * g.height * g.width
-        _prof.append((e0, e1, "conv3_thin_kernel" if mt == 16 else "conv3x3_kernel", fl, 2.0 * 9 * cin * cout * g.np))
+    co = cout if cout_valid is None else cout_valid
+    with _profiled("conv3_thin_kernel" if mt == 16 else "conv3x3_kernel", _conv_flops(g, cin, co), 2.0 * 9 * cin * cout * g.np):
+        check(_l().dinv_conv3x3_bias(ctypes.byref(g), ptr(x), ptr(wpk), ptr(bias), cin, cout, co, mt, ptr(y), ptr(res1), int(relu),
+                                     stream_ptr(y.device)))
 
 
 def conv3x3_winograd4_bias(g, x, wino4, bias, cin, cout, y, relu=False, workspace=None):
     """y = [relu](conv3x3(x) + bias) via Winograd F(4x4,3x3) (csrc/drunet_wino4.hip, bias in the epilogue); wino4 from
     pack_winograd4_weight; height and width multiples of 4"""
-    if _prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_l().dinv_conv3x3_winograd4_bias(ctypes.byref(g), ptr(x), ptr(wino4), ptr(bias), cin, cout, ptr(y), int(relu),
-                                           ptr(workspace), 0 if workspace is None else workspace.numel(), stream_ptr(y.device)))
-    if _prof is not None:
-        e1.record()
-        tiles = g.batch * (g.height // 4) * (g.width // 4)
-        _prof.append((e0, e1, "conv3x3_wino4_kernel", 2.0 * 9 * cin * cout * g.batch * g.height * g.width,
-                      2.0 * 36 * cin * cout * tiles))
+    tiles = g.batch * (g.height // 4) * (g.width // 4)
+    with _profiled("conv3x3_wino4_kernel", _conv_flops(g, cin, cout), 2.0 * 36 * cin * cout * tiles):
+        check(_l().dinv_conv3x3_winograd4_bias(ctypes.byref(g), ptr(x), ptr(wino4), ptr(bias), cin, cout, ptr(y), int(relu),
+                                               ptr(workspace), 0 if workspace is None else workspace.numel(), stream_ptr(y.device)))
 
 
 def conv3x3_tail_bias(g, x, wtail, bias, cin, cout, y, res=None):
     """last layer on the vector ALU: y[:cout] = conv3x3(x) + bias (+ res, first channel block); wtail from pack_tail_weight"""
-    if _prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_l().dinv_conv3x3_tail_bias(ctypes.byref(g), ptr(x), ptr(wtail), ptr(bias), cin, cout, ptr(y), ptr(res), stream_ptr(y.device)))
-    if _prof is not None:
-        e1.record()
-        fl = 2.0 * 9 * cin * cout * g.batch * g.height * g.width
-        _prof.append((e0, e1, "tail3x3_shift_kernel", fl, 0.0))
+    with _profiled("tail3x3_shift_kernel", _conv_flops(g, cin, cout), 0.0):
+        check(_l().dinv_conv3x3_tail_bias(ctypes.byref(g), ptr(x), ptr(wtail), ptr(bias), cin, cout, ptr(y), ptr(res), stream_ptr(y.device)))
 
 
 def bias_grad(g, gy, c, db=None, accumulate=False):

@@ -24,18 +24,13 @@ from torch.autograd.function import once_differentiable
 from .. import hip as H
 from ..hip import drunet as K
 from .base import Denoiser
-from .drunet import DRUNet
+from .unet_autograd import _flip_t
 
 
 def weights_init_kaiming(m):
     """deepinv/models/dncnn.py: Kaiming-normal weights (fan_in), biases keep PyTorch's default"""
     if m.__class__.__name__.find("Conv") != -1:
         nn.init.kaiming_normal_(m.weight.data, a=0, mode="fan_in")
-
-
-def _flip_t(w):
-    """filter of the data-gradient convolution: [Cout,Cin,3,3] -> [Cin,Cout,3,3], taps reversed"""
-    return w.flip(2, 3).transpose(0, 1).contiguous()
 
 
 class DnCNN(Denoiser):
@@ -99,12 +94,8 @@ class DnCNN(Denoiser):
         return self._hip_forward(x)
 
     # ------------------------------------------------------------------ inference engine
-    def _weights_version(self):
-        return (tuple(0 if p.is_inference() else p._version for p in self.parameters())
-                + tuple(p.data_ptr() for p in self.parameters()))
-
     def _prepare(self, device):
-        ver = self._weights_version()
+        ver = K.weights_version(self)
         if self._engine is not None and self._engine["ver"] == ver and self._engine["device"] == device:
             return self._engine
         e = {"ver": ver, "device": device, "ws": {}}
@@ -151,14 +142,10 @@ class DnCNN(Denoiser):
         return y
 
 
-# ---- layer helpers: a "pack" is (p64, p32, bias) with p64 / p32 = pack_conv3x3_weight tuples (64- / 32-wide cout tiles)
-# and bias the zero-padded fp32 bias (None for bias=False)
+# ---- layer helpers: a "pack" is a K.ConvPacks with the direct packs (64- / 32-wide cout tiles) and the zero-padded fp32 bias
+# (None for bias=False)
 def _direct_packs(m, device):
-    w = m.weight.to(device)
-    p64 = K.pack_conv3x3_weight(w)
-    p32 = K.pack_conv3x3_weight(w, mt=32) if p64[0].shape[3] == 64 else p64
-    b = K.pack_bias(m.bias.to(device), p64[2]) if m.bias is not None else None
-    return (p64, p32, b)
+    return K.conv_packs(m.weight.to(device), m.bias.to(device) if m.bias is not None else None)
 
 
 def _tail_pack(m, device):
@@ -176,17 +163,16 @@ def _tail_pack(m, device):
 
 def _layer(g, pk, x, y, cout, relu=False, res1=None):
     """y = [relu](conv(x) + b) (+res1) on the direct fp32 kernel (the bias-free kernel when there is no bias)"""
-    (w, ci, co) = DRUNet._pick(g, pk)
-    if pk[2] is not None:
-        K.conv3x3_bias(g, x, w, pk[2], ci, co, y, cout_valid=cout, res1=res1, relu=relu)
+    if pk.bias is not None:
+        K.conv3x3_bias(g, x, pk.pick(g), pk.bias, pk.cin_p, pk.cout_p, y, cout_valid=cout, res1=res1, relu=relu)
     else:
-        K.conv3x3(g, x, w, ci, co, y, cout_valid=cout, res1=res1, relu=relu)
+        K.conv3x3(g, x, pk.pick(g), pk.cin_p, pk.cout_p, y, cout_valid=cout, res1=res1, relu=relu)
 
 
 def _winograd(g, pk, wino, x, y, nf):
     wsp = K.winograd4_workspace(x.device)
-    if pk[2] is not None:
-        K.conv3x3_winograd4_bias(g, x, wino, pk[2], nf, nf, y, relu=True, workspace=wsp)
+    if pk.bias is not None:
+        K.conv3x3_winograd4_bias(g, x, wino, pk.bias, nf, nf, y, relu=True, workspace=wsp)
     else:
         K.conv3x3_winograd4(g, x, wino, nf, nf, y, relu=True, workspace=wsp)
 
@@ -294,5 +280,5 @@ class _Holder:
 
 def _fwd_pack(w, b, kind, flip=False):
     """direct-kernel packs of a (flipped) weight, cached per weight tensor and version; the bias is packed per call (a few floats)"""
-    p64, p32, _ = K.cached_pack((kind, flip), w, lambda: _direct_packs(_Holder(_flip_t(w) if flip else w, None), w.device))
-    return (p64, p32, K.pack_bias(b, p64[2]) if b is not None else None)
+    pk = K.cached_pack((kind, flip), w, lambda: K.conv_packs(_flip_t(w) if flip else w))
+    return pk._replace(bias=K.pack_bias(b, pk.cout_p)) if b is not None else pk

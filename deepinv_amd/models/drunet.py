@@ -214,31 +214,17 @@ class DRUNet(Denoiser):
         return run_four_windows(run, xin, field=64)
 
     # ------------------------------------------------------------------ MFMA inference engine
-    def _weights_version(self):
-        # tensors created under torch.inference_mode() carry no version counter (reading it raises)
-        return (tuple(0 if p.is_inference() else p._version for p in self.parameters())
-                + tuple(p.data_ptr() for p in self.parameters()))
-
     def _prepare(self, device):
-        ver = (self._weights_version(), self._precision(), K.FP32_WINOGRAD4_BF16X3)     # the packs depend on the precision
+        ver = (K.weights_version(self), self._precision(), K.FP32_WINOGRAD4_BF16X3)     # the packs depend on the precision
         if self._engine is not None and self._engine["ver"] == ver and self._engine["device"] == device:
             return self._engine
         e = {"ver": ver, "device": device, "ws": {}, "split": self._precision() == "bf16split"}
         split = e["split"]
 
         def c3(m):
-            """packs of one 3x3 conv: direct fp32 (64- and 32-wide cout tiles; _pick() chooses per launch geometry) and, per
-            precision, the bf16-split pack or the fp32 Winograd pack"""
-            w = m.weight.to(device)
-            p64 = K.pack_conv3x3_weight(w)
-            p32 = K.pack_conv3x3_weight(w, mt=32) if p64[0].shape[3] == 64 else p64
-            ok = w.shape[0] % 64 == 0 and w.shape[1] % 16 == 0
-            s2d = K.pack_split2d_weight(w) if (split and ok) else None
-            wino = K.pack_winograd_weight(w) if (not split and ok and w.shape[1] >= 32) else None
-            wsp = K.pack_wsplit_weight(w) if (split and ok) else None
-            wino4 = K.pack_winograd4_weight(w) if (not split and ok) else None
-            wino4x3 = K.pack_winograd4_bf16x3_weight(w) if (not split and ok and K.FP32_WINOGRAD4_BF16X3) else None
-            return (p64, p32, wino, s2d, wsp, wino4, wino4x3)
+            """packs of one 3x3 conv: direct fp32 (64- and 32-wide cout tiles; ConvPacks.pick chooses per launch geometry) and, per
+            precision, the bf16-split packs or the fp32 Winograd packs"""
+            return K.conv_packs(m.weight.to(device), precision=self._precision())
 
         e["head"] = c3(self.m_head)
         e["tail"] = c3(self.m_tail)
@@ -272,8 +258,7 @@ class DRUNet(Denoiser):
                 e["ws"].clear()  # one image geometry at a time keeps the footprint bounded (its batch lanes live side by side)
             nc = self.nc
             g = [K.geom(B, H >> i, W >> i) for i in range(4)]
-            cin_p = e["head"][0][1]
-            ws = {"g": g, "in": K.alloc(g[0], cin_p, device), "out": K.alloc(g[0], self.out_channels, device)}
+            ws = {"g": g, "in": K.alloc(g[0], e["head"].cin_p, device), "out": K.alloc(g[0], self.out_channels, device)}
             for i in range(4):
                 # skip tensor x_{i+1}, two ping-pong buffers and the ResBlock temporary
                 for nm in ("skip", "a", "b", "t"):
@@ -281,48 +266,39 @@ class DRUNet(Denoiser):
             e["ws"][key] = ws
         return ws
 
-    @staticmethod
-    def _pick(g, packs):
-        """64-wide cout tiles unless that grid would leave the chip under-filled (< 3 rounds of the 512 resident
-        workgroup slots): then 32-wide tiles double the number of workgroups (small per-GPU batches)."""
-        p64, p32 = packs[:2]
-        if p64[0].shape[3] == 64 and ((g.np + 255) // 256) * (p64[2] // 64) < 1536:
-            return p32
-        return p64
-
     def _conv_fp32(self, g, pk, x, y, relu=False, res1=None):
         """one ResBlock convolution in fp32 arithmetic: Winograd F(4x4,3x3) kernel (csrc/drunet_wino4.hip) where the image
         sides are multiples of 4 and the launch has enough 64-cout x 32-tile workgroup tiles to occupy the chip, else the
         F(2x2,3x3) kernel, else the direct MFMA kernel"""
-        if (pk[5] is not None and K.FP32_WINOGRAD_TILE == 4 and g.height % 4 == 0 and g.width % 4 == 0
-                and -(-g.batch * (g.height // 4) * (g.width // 4) // 32) * (pk[0][2] // 64) >= K.WINOGRAD4_MIN_TILES):
+        ci, co = pk.cin_p, pk.cout_p
+        # workgroup tiles (64 couts x 32 tile positions) of the F(4x4) launch
+        tiles = -(-g.batch * (g.height // 4) * (g.width // 4) // 32) * (co // 64)
+        if (pk.wino4 is not None and K.FP32_WINOGRAD_TILE == 4 and g.height % 4 == 0 and g.width % 4 == 0
+                and tiles >= K.WINOGRAD4_MIN_TILES):
             # inside a batch lane the last, incomplete round of tiles is left to the other lane (see batch_lanes) - unless the
             # WHOLE launch is less than one round (fewer tiles than compute units: the deep levels of a small lane), where cutting
             # the tiles along the input channels is what fills the chip
-            tiles = -(-g.batch * (g.height // 4) * (g.width // 4) // 32) * (pk[0][2] // 64)
             wsp = K.winograd4_workspace(x.device) if (self._tail_split or tiles < _compute_units(x.device)) else None
-            if pk[6] is not None:       # (K.FP32_WINOGRAD4_BF16X3 when the packs were built)
-                K.conv3x3_winograd4_bf16x3(g, x, pk[6], pk[0][1], pk[0][2], y, res1=res1, relu=relu, workspace=wsp)
+            if pk.wino4x3 is not None:       # (K.FP32_WINOGRAD4_BF16X3 when the packs were built)
+                K.conv3x3_winograd4_bf16x3(g, x, pk.wino4x3, ci, co, y, res1=res1, relu=relu, workspace=wsp)
             else:
-                K.conv3x3_winograd4(g, x, pk[5], pk[0][1], pk[0][2], y, res1=res1, relu=relu, workspace=wsp)
-            return
-        if pk[2] is not None:
-            K.conv3x3_winograd(g, x, pk[2], pk[0][1], pk[0][2], y, res1=res1, relu=relu)
-            return
-        (w, ci, co) = self._pick(g, pk)
-        K.conv3x3(g, x, w, ci, co, y, relu=relu, res1=res1)
+                K.conv3x3_winograd4(g, x, pk.wino4, ci, co, y, res1=res1, relu=relu, workspace=wsp)
+        elif pk.wino2 is not None:
+            K.conv3x3_winograd(g, x, pk.wino2, ci, co, y, res1=res1, relu=relu)
+        else:
+            K.conv3x3(g, x, pk.pick(g), ci, co, y, relu=relu, res1=res1)
 
     def _res_block(self, g, pk1, pk2, x, t, y):
         """y = x + conv2(relu(conv1(x))) (drunet.py:403-434); `t` is scratch.  bf16-split precision: Winograd F(2,3) along
         rows on the bf16 matrix cores (csrc/drunet_wsplit.hip: 1.5x fewer matrix instructions, measured 12-25 % faster per
         level at 4 and 32 slices) wherever the image width is even; else the direct kernel, whose conv1 writes its ReLU output
         pre-split (the parts conv2 would form anyway) so that conv2 stages it by plain copies"""
-        if pk1[4] is not None and pk2[4] is not None and g.width % 2 == 0:
-            K.conv3x3_wsplit(g, x, pk1[4], pk1[0][1], pk1[0][2], t, relu=True)
-            K.conv3x3_wsplit(g, t, pk2[4], pk2[0][1], pk2[0][2], y, res1=x)
-        elif pk1[3] is not None and pk2[3] is not None:
-            K.conv3x3_split(g, x, pk1[3], pk1[0][1], pk1[0][2], t, relu=True, y_presplit=True)
-            K.conv3x3_split(g, t, pk2[3], pk2[0][1], pk2[0][2], y, res1=x, x_presplit=True)
+        if pk1.wsplit is not None and pk2.wsplit is not None and g.width % 2 == 0:
+            K.conv3x3_wsplit(g, x, pk1.wsplit, pk1.cin_p, pk1.cout_p, t, relu=True)
+            K.conv3x3_wsplit(g, t, pk2.wsplit, pk2.cin_p, pk2.cout_p, y, res1=x)
+        elif pk1.split2d is not None and pk2.split2d is not None:
+            K.conv3x3_split(g, x, pk1.split2d, pk1.cin_p, pk1.cout_p, t, relu=True, y_presplit=True)
+            K.conv3x3_split(g, t, pk2.split2d, pk2.cin_p, pk2.cout_p, y, res1=x, x_presplit=True)
         else:
             self._conv_fp32(g, pk1, x, t, relu=True)
             self._conv_fp32(g, pk2, t, y, res1=x)
@@ -445,8 +421,8 @@ class DRUNet(Denoiser):
         nc = self.nc
         x = x.contiguous().float()
         K.pack_input(g[0], x, sigma_map, ws["in"])
-        (wh, cih, coh) = self._pick(g[0], e["head"])
-        K.conv3x3(g[0], ws["in"], wh, cih, coh, ws["skip0"], cin_valid=self.in_channels + 1)  # x1
+        hd = e["head"]
+        K.conv3x3(g[0], ws["in"], hd.pick(g[0]), hd.cin_p, hd.cout_p, ws["skip0"], cin_valid=self.in_channels + 1)  # x1
         cur = ws["skip0"]
         downs = ("m_down1", "m_down2", "m_down3")
         for i, name in enumerate(downs):
@@ -471,8 +447,8 @@ class DRUNet(Denoiser):
         if e["tail_valu"] is not None:   # m_tail(x + x1)
             K.conv3x3_tail(g[0], r, e["tail_valu"], nc[0], self.out_channels, ws["out"], x2=ws["skip0"])
         else:
-            (wt, cit, cot) = self._pick(g[0], e["tail"])
-            K.conv3x3(g[0], r, wt, cit, cot, ws["out"], cout_valid=self.out_channels, x2=ws["skip0"])
+            tl = e["tail"]
+            K.conv3x3(g[0], r, tl.pick(g[0]), tl.cin_p, tl.cout_p, ws["out"], cout_valid=self.out_channels, x2=ws["skip0"])
         y = out if out is not None else torch.empty((B, self.out_channels, H, W), device=dev, dtype=torch.float32)
         K.unpack_output(g[0], ws["out"], self.out_channels, y)
         return y

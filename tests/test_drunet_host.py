@@ -140,7 +140,7 @@ def test_res_block_dispatch_even_and_odd_widths(monkeypatch):
                         gate=False: calls.append(("split", relu, res1 is not None, x_presplit, y_presplit)))
     model = D.DRUNet.__new__(D.DRUNet)
     model._conv_fp32 = lambda g, pk, x, y, relu=False, res1=None: calls.append(("fp32", relu, res1 is not None))
-    pk = ((None, 64, 64), None, None, "s2d", "wsp")
+    pk = D.K.ConvPacks(None, None, 64, 64, split2d="s2d", wsplit="wsp")
     x = t = y = object()
     model._res_block(types.SimpleNamespace(width=40), pk, pk, x, t, y)
     assert calls == [("wsplit", True, False), ("wsplit", False, True)]
@@ -148,7 +148,7 @@ def test_res_block_dispatch_even_and_odd_widths(monkeypatch):
     model._res_block(types.SimpleNamespace(width=5), pk, pk, x, t, y)
     assert calls == [("split", True, False, False, True), ("split", False, True, True, False)]
     calls.clear()
-    none = ((None, 64, 64), None, None, None, None)
+    none = D.K.ConvPacks(None, None, 64, 64)
     model._res_block(types.SimpleNamespace(width=40), none, none, x, t, y)
     assert calls == [("fp32", True, False), ("fp32", False, True)]
 
