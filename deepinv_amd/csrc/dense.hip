@@ -1,0 +1,187 @@
+// out[I, R] = in[I, K] M^T on the fp32 matrix cores (gfx950): the three operators of CompressedSensing.
+//
+// Replaces the ATen launches behind
+//   CompressedSensing.A / A_adjoint / A_dagger     deepinv/physics/compressed_sensing.py:126-166 (torch.einsum("in, mn->im"))
+//
+// The regime is few rows (I = the batch, 1 to a few tens) against a matrix of hundreds to thousands of rows and columns: the call
+// is bound by streaming M from HBM once, so the layout follows M.
+//   transposed = 0   out[i, r] = sum_k in[i, k] M[r, k]     M is [R, K], row stride ldm
+//   transposed = 1   out[i, r] = sum_k in[i, k] M[k, r]     M is [K, R], row stride ldm  (A_adjoint reads _A itself)
+//
+// dense_partial_kernel: one wave owns 32 output columns r, one slice of K and up to 32 NI input rows, and accumulates
+// v_mfma_f32_32x32x2_f32 with the input rows on the A side and the rows of M on the B side.  Lane l supplies row (l & 31) and the
+// 16 consecutive k's of half (l >> 5) of a block of 32: for transposed = 0 that is 64 contiguous bytes of a row of M per lane
+// (four 16-byte loads where the row is aligned), for transposed = 1 sixteen loads that each cover 128 contiguous bytes per half
+// wave.  Which k a lane supplies to which MFMA is free as long as both operands agree, so no value is shuffled.  Edges (I, K, R of
+// any size) are zero-filled in registers; M is never copied.
+// K is split over gridDim.y slices so that more than R / 32 waves stream M; every slice writes its partial tile to the workspace
+// [S, I, R] and dense_reduce_kernel adds the slices in index order: no atomics, bit-reproducible.  One slice writes `out` itself.
+#include "common.hpp"
+
+using namespace dinv;
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kTile = 32;       // rows of M (output columns) per wave, and input rows per accumulator
+constexpr int kBlockK = 32;     // k's per step: 16 per half wave
+constexpr int kMaxNI = 4;       // accumulators per wave: up to 128 input rows stream M once
+constexpr int kTargetWaves = 1024;  // 4 per compute unit of an MI355X
+constexpr int kMinSliceK = 64;
+
+struct DenseArgs {
+    const float* in;
+    const float* M;
+    float* dst;          // out, or the workspace [S, I, R]
+    int64_t I, K, R, ldm;
+    int64_t kchunk;      // k's per slice, a multiple of kBlockK
+    int transposed;
+    int vec_in, vec_m;   // 16-byte loads along k are aligned
+};
+
+// 16 consecutive floats of a row, zero past `avail`
+__device__ __forceinline__ void load_row16(const float* __restrict__ p, int64_t avail, bool vec, float (&v)[16]) {
+    if (vec && avail >= 16) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 f = reinterpret_cast<const float4*>(p)[q];
+            v[4 * q] = f.x; v[4 * q + 1] = f.y; v[4 * q + 2] = f.z; v[4 * q + 3] = f.w;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) v[q] = q < avail ? p[q] : 0.f;
+    }
+}
+
+template <int NI>
+__global__ __launch_bounds__(64) void dense_partial_kernel(DenseArgs a) {
+    const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
+    const int64_t r = (int64_t)blockIdx.x * kTile + j;
+    const int64_t s = blockIdx.y;
+    const int64_t i0 = (int64_t)blockIdx.z * kTile * NI;
+    const int64_t kbeg = s * a.kchunk;
+    const int64_t kend = kbeg + a.kchunk < a.K ? kbeg + a.kchunk : a.K;
+    // NA independent accumulators per tile of input rows, fed in turn and added at the end: back-to-back MFMAs never wait on
+    // each other's result, and the chain of roundings of one sum is NA times shorter
+    constexpr int NA = kMaxNI / NI;
+    f32x16 acc[NI][NA];
+#pragma unroll
+    for (int t = 0; t < NI; ++t)
+#pragma unroll
+        for (int u = 0; u < NA; ++u)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[t][u][e] = 0.f;
+    for (int64_t k0 = kbeg; k0 < kend; k0 += kBlockK) {
+        const int64_t k = k0 + 16 * h;
+        const int64_t avail = kend - k;      // may be <= 0 for the upper half of the last block
+        float mv[16];
+        if (r >= a.R || avail <= 0) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) mv[q] = 0.f;
+        } else if (!a.transposed) {
+            load_row16(a.M + r * a.ldm + k, avail, a.vec_m != 0, mv);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) mv[q] = q < avail ? a.M[(k + q) * a.ldm + r] : 0.f;
+        }
+#pragma unroll
+        for (int t = 0; t < NI; ++t) {
+            const int64_t i = i0 + t * kTile + j;
+            float xv[16];
+            if (i >= a.I || avail <= 0) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q) xv[q] = 0.f;
+            } else {
+                load_row16(a.in + i * a.K + k, avail, a.vec_in != 0, xv);
+            }
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[t][q % NA] = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[q], mv[q], acc[t][q % NA], 0, 0, 0);
+        }
+    }
+    // D element e of lane l: row (e & 3) + 8 (e >> 2) + 4 (l >> 5) (an input row), column l & 31 (a row of M)
+    if (r < a.R) {
+        float* dst = a.dst + s * a.I * a.R;
+#pragma unroll
+        for (int t = 0; t < NI; ++t)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int64_t i = i0 + t * kTile + (e & 3) + 8 * (e >> 2) + 4 * h;
+                float v = acc[t][0][e];
+                if constexpr (NA == 4) v = (v + acc[t][1][e]) + (acc[t][2][e] + acc[t][3][e]);
+                if constexpr (NA == 2) v = v + acc[t][1][e];
+                if (i < a.I) dst[i * a.R + r] = v;
+            }
+    }
+}
+
+__global__ __launch_bounds__(256) void dense_reduce_kernel(const float* __restrict__ ws, float* __restrict__ out, int64_t total, int S) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        float v = ws[e];
+        for (int s = 1; s < S; ++s) v += ws[(int64_t)s * total + e];
+        out[e] = v;
+    }
+}
+
+// slices of K: enough waves for the chip, none shorter than kMinSliceK, each a multiple of kBlockK.  A function of the shape only.
+void split_k(int64_t I, int64_t K, int64_t R, int64_t* S, int64_t* kchunk) {
+    const int64_t tiles = ceil_div(R, kTile) * ceil_div(I, (int64_t)kTile * kMaxNI);
+    int64_t s = kTargetWaves / tiles;
+    const int64_t most = ceil_div(K, kMinSliceK);
+    if (s > most) s = most;
+    if (s < 1) s = 1;
+    const int64_t c = ceil_div(ceil_div(K, s), kBlockK) * kBlockK;
+    *kchunk = c;
+    *S = ceil_div(K, c);
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" size_t dinv_dense_workspace_bytes(int64_t I, int64_t K, int64_t R) {
+    if (I < 1 || K < 1 || R < 1) return 0;
+    int64_t S, kchunk;
+    split_k(I, K, R, &S, &kchunk);
+    return S > 1 ? (size_t)S * I * R * sizeof(float) : 0;
+}
+
+extern "C" int dinv_dense_apply(const float* in, const float* M, float* out, int64_t I, int64_t K, int64_t R, int64_t ldm,
+                                int32_t transposed, void* workspace, size_t workspace_bytes, dinv_stream_t stream) {
+    DINV_REQUIRE(I >= 0 && K >= 1 && R >= 1, "dense: bad shape I = %lld, K = %lld, R = %lld", (long long)I, (long long)K, (long long)R);
+    if (I == 0) return 0;
+    DINV_REQUIRE(in && M && out && in != out, "dense: operands must be non-null and out must not alias in");
+    DINV_REQUIRE(ldm >= (transposed ? R : K), "dense: row stride %lld of M is below its row length %lld", (long long)ldm,
+                 (long long)(transposed ? R : K));
+    DINV_REQUIRE(I * R < ((int64_t)1 << 40) && K < ((int64_t)1 << 31) && R < ((int64_t)1 << 31), "dense: shape too large");
+    int64_t S, kchunk;
+    split_k(I, K, R, &S, &kchunk);
+    const size_t need = S > 1 ? (size_t)S * I * R * sizeof(float) : 0;
+    DINV_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "dense: the workspace holds %zu bytes, %zu are needed "
+                 "(dinv_dense_workspace_bytes)", workspace_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    DenseArgs a{};
+    a.in = in; a.M = M;
+    a.dst = S > 1 ? (float*)workspace : out;
+    a.I = I; a.K = K; a.R = R; a.ldm = ldm; a.kchunk = kchunk;
+    a.transposed = transposed ? 1 : 0;
+    a.vec_in = aligned16(in) && K % 4 == 0;
+    a.vec_m = !transposed && aligned16(M) && ldm % 4 == 0;
+    const int64_t per = (int64_t)kTile * kMaxNI;
+    const int ni = I > 2 * kTile ? 4 : (I > kTile ? 2 : 1);
+    const int64_t chunks = ni == 4 ? ceil_div(I, per) : 1;
+    DINV_REQUIRE(chunks < 65536 && S < 65536, "dense: too many row chunks");
+    const dim3 grid((unsigned)ceil_div(R, kTile), (unsigned)S, (unsigned)chunks);
+    if (ni == 4) hipLaunchKernelGGL(dense_partial_kernel<4>, grid, dim3(64), 0, st, a);
+    else if (ni == 2) hipLaunchKernelGGL(dense_partial_kernel<2>, grid, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(dense_partial_kernel<1>, grid, dim3(64), 0, st, a);
+    DINV_CHECK_LAUNCH();
+    if (S > 1) {
+        const int64_t total = I * R;
+        const int64_t blocks = ceil_div(total, 256);
+        hipLaunchKernelGGL(dense_reduce_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, st,
+                           (const float*)workspace, out, total, (int)S);
+        DINV_CHECK_LAUNCH();
+    }
+    return 0;
+}

@@ -5,6 +5,8 @@ from .mri import MRI, MultiCoilMRI, MRIMixin
 from .tomography import Tomography, RampFilter
 from .blur import Blur, BlurFFT, Downsampling
 from .singlepixel import SinglePixelCamera
+from .compressed_sensing import CompressedSensing
+from .structured_random import StructuredRandom
 from . import functional
 from . import singlepixel
 from . import generator

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from ..hip import conv as hc
+from ..hip import dst as hdst
 from ..hip import fft as hfft
 
 
@@ -309,3 +310,10 @@ def bicubic_filter(factor=2, device="cpu"):
     w = w + (a * x.pow(3) - 5 * a * x.pow(2) + 8 * a * x - 4 * a) * (x > 1) * (x < 2)
     w = torch.outer(w, w)
     return (w / w.sum())[None, None]
+
+
+def dst1(x):
+    r"""Orthogonal discrete sine transform, type I, of the last dimension, with the reference's sign
+    (deepinv/physics/compressed_sensing.py:9-29): :math:`-\sqrt{2/(n+1)} \sum_j x_j \sin(\pi (j+1)(k+1)/(n+1))`.  It is
+    symmetric and ``dst1(dst1(x)) = x``.  One launch of csrc/dst.hip for any leading shape; fp32."""
+    return hdst.dst1(x)

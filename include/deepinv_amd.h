@@ -35,7 +35,7 @@ typedef void* dinv_stream_t; /* hipStream_t */
 /* library / error                                                            */
 /* ------------------------------------------------------------------------- */
 const char* dinv_last_error(void);
-int dinv_version(void);   /* 14 = this header (adds dinv_poisson_noise and dinv_fidelity_pointwise); 13: (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
+int dinv_version(void);   /* 15 = this header (adds the DST-I / StructuredRandom entry points dinv_dst1, dinv_structured_apply and the dense fp32 product dinv_dense_apply); 14: (adds dinv_poisson_noise and dinv_fidelity_pointwise); 13: (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
 /* number of visible HIP devices (0 when no GPU): used by the host to fail loudly */
 int dinv_device_count(int* count);
 
@@ -718,6 +718,45 @@ int dinv_hadamard(const float* x, float* out, int64_t P, int32_t H, int32_t W, i
 int dinv_hadamard_apply(const float* x, const float* y, const float* mask, float* out, int64_t P, int32_t H, int32_t W,
                         int64_t mask_planes, int32_t flags, float add, float scale, void* ws, size_t ws_bytes,
                         dinv_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
+/* DST-I, StructuredRandom and CompressedSensing (deepinv/physics/compressed_sensing.py:9-29, 126-166; structured_random.py:172-202) */
+/* ------------------------------------------------------------------------- */
+/* fp32 only, contiguous operands.  dst1 is the reference's transform of the last axis,
+ *     dst1(x)_k = -sqrt(2 / (n + 1)) sum_j x_j sin(pi (j + 1)(k + 1) / (n + 1)),
+ * symmetric and its own inverse, computed by the in-LDS FFT engine on the odd extension of length 2 (n + 1), two rows per complex
+ * transform.  `plan` / `table` come from dinv_fft_plan_init(2 (n + 1)) (the table on the device).  n <= DINV_DST_MAX_N: above it the
+ * tables and the two line buffers of one pair of rows exceed the 160 KB of LDS of a workgroup and the call returns an error.
+ * No workspace (dinv_dst_workspace_bytes returns 0), no atomics, bit-reproducible.
+ *
+ * dinv_dst1: out[rows, n] = dst1(x[rows, n]).  x == out is allowed.
+ *
+ * dinv_structured_apply: the whole of StructuredRandom.A (adjoint = 0) or A_adjoint (adjoint = 1) as ONE launch for any number of
+ * layers.  x is [planes, H_in, W_in], out [planes, H_out, W_out], the working size (H_work, W_work) is the larger of the two and
+ * the smaller side sits at rows top .., columns left .. of it (the reference's centred pad / trim: ceil of half the difference).
+ *     A          [F if half]  then  F D_i  for i = 0 .. layers - 1           F = dst1 along W_work
+ *     A_adjoint  D_{layers-1-i} F  for i = 0 .. layers - 1,  then  [F if half]
+ * `diag` is [layers, diag_rows, W_work]; work row r (over all planes, r = plane * H_work + h) uses diagonal row r % diag_rows
+ * (diag_rows = C * H_work for a [C, H, W] image shared by the batch).  Every row is loaded once, stays in LDS through all layers
+ * and is stored once; rows of a padded output that correspond to no input row are written as zeros without a transform, trimmed
+ * rows are never read.  layers + half >= 1.  x must not alias out. */
+#define DINV_DST_MAX_N 2924
+size_t dinv_dst_workspace_bytes(int64_t rows, int32_t n);
+int dinv_dst1(const float* x, float* out, int64_t rows, int32_t n, const dinv_fft_plan* plan, const void* table_dev,
+              dinv_stream_t stream);
+int dinv_structured_apply(const float* x, float* out, const float* diag, int64_t planes, int32_t H_in, int32_t W_in,
+                          int32_t H_out, int32_t W_out, int32_t H_work, int32_t W_work, int32_t top, int32_t left,
+                          int64_t diag_rows, int32_t layers, int32_t half, int32_t adjoint, const dinv_fft_plan* plan,
+                          const void* table_dev, dinv_stream_t stream);
+
+/* dinv_dense_apply: out[I, R] = sum_k in[i, k] M[r, k] (transposed = 0, M is [R, K]) or sum_k in[i, k] M[k, r] (transposed = 1, M is
+ * [K, R]); ldm is the row stride of M in floats.  fp32 MFMA with fp32 accumulation.  Any I, K, R: edges are handled in the kernel.
+ * M is read once per 128 rows of `in`.  K is split over workgroups and the partial sums are added in slice order from
+ * `workspace` (dinv_dense_workspace_bytes(I, K, R) bytes; 0 means none is needed and null is accepted): no atomics,
+ * bit-reproducible.  out must not alias in. */
+size_t dinv_dense_workspace_bytes(int64_t I, int64_t K, int64_t R);
+int dinv_dense_apply(const float* in, const float* M, float* out, int64_t I, int64_t K, int64_t R, int64_t ldm,
+                     int32_t transposed, void* workspace, size_t workspace_bytes, dinv_stream_t stream);
 
 #ifdef __cplusplus
 }

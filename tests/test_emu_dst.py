@@ -1,0 +1,257 @@
+"""DST-I kernel (deepinv_amd/csrc/dst.hip) on the host emulation: the bare transform and the fused StructuredRandom operator
+against a float64 restatement written here - the dense sine matrix with the reference's sign,
+``S[j, k] = -sqrt(2 / (n + 1)) sin(pi (j + 1)(k + 1) / (n + 1))``, with pad, diagonals and trim composed around it.
+
+Bound against fp64: twice the reference's own fp32 error (``K__err`` of tests/golden/compressed_sensing.npz) where a golden
+case of the same shape exists.  Elsewhere (n = 100 and 1024, the row-count cases) the worst-case rounding of the arithmetic: a
+radix-r butterfly stage of the FFT of length P = 2 (n + 1) rounds one twiddle product (the rounded twiddle, the products and
+their sum: at most 3 u relative) and r - 1 additions per output, so it adds at most (r + 3) u to the relative l2 error (radix 4
+and 8 are two and three radix-2 levels); the final scale and a diagonal add one u each.  One transform is therefore within
+(sum_stages (r + 3) + 2) u and an operator with T transforms within T times that, u = 2^-24."""
+import ctypes
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import emu_lib as E
+
+EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
+TARGET = "libdeepinv_amd_emu_dst.so"
+GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "compressed_sensing.npz"))
+U = 2.0 ** -24
+MAX_N = 2924
+_lib = None
+_plans = {}
+
+
+def lib():
+    """fft.hip (plans, dinv_last_error) + dst.hip built for the host by tests/emu/Makefile, as a library of their own"""
+    global _lib
+    if _lib is None:
+        subprocess.run(["make", "-C", EMU_DIR, "-j4", "SRCS=fft dst", f"TARGET={TARGET}"], check=True, stdout=subprocess.DEVNULL)
+        l = ctypes.CDLL(os.path.join(EMU_DIR, TARGET))
+        l.dinv_last_error.restype = ctypes.c_char_p
+        vp, i32, i64, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
+        plan = ctypes.POINTER(E.FftPlan)
+        l.dinv_fft_table_bytes.restype = sz
+        l.dinv_fft_table_bytes.argtypes = [i32]
+        l.dinv_fft_plan_init.argtypes = [i32, plan, vp]
+        l.dinv_dst_workspace_bytes.restype = sz
+        l.dinv_dst_workspace_bytes.argtypes = [i64, i32]
+        l.dinv_dst1.argtypes = [vp, vp, i64, i32, plan, vp, vp]
+        l.dinv_structured_apply.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i64, i32, i32, i32, plan, vp, vp]
+        _lib = l
+    return _lib
+
+
+def plan_for(n):
+    P = 2 * (n + 1)
+    if P not in _plans:
+        l = lib()
+        plan = E.FftPlan()
+        table = np.zeros(l.dinv_fft_table_bytes(P), np.uint8)
+        assert l.dinv_fft_plan_init(P, ctypes.byref(plan), E.p(table)) == 0
+        _plans[P] = (plan, table)
+    return _plans[P]
+
+
+def derived(n, transforms=1, diagonals=0):
+    plan, _ = plan_for(n)
+    cost = {4: 10, 8: 15}
+    per = sum(cost.get(r, r + 3) for r in plan.radix[:plan.nstages]) + 2
+    return (transforms * per + diagonals) * U
+
+
+def dst1(x):
+    n = x.shape[-1]
+    plan, table = plan_for(n)
+    out = torch.full_like(x, float("nan"))
+    rc = lib().dinv_dst1(E.p(x), E.p(out), x.numel() // n, n, ctypes.byref(plan), E.p(table), None)
+    assert rc == 0, lib().dinv_last_error()
+    return out
+
+
+def sine(n):
+    j = torch.arange(1, n + 1, dtype=torch.float64)
+    return -math.sqrt(2.0 / (n + 1)) * torch.sin(math.pi * j[:, None] * j[None, :] / (n + 1))
+
+
+def rel(a, b):
+    return float((a.double() - b).norm() / b.norm().clamp_min(1e-300))
+
+
+# ---------------------------------------------------------------- the bare transform
+@pytest.mark.parametrize("n", [int(n) for n in GOLD["dst_n"]])
+def test_dst1_golden_lengths(n):
+    x = torch.from_numpy(GOLD[f"dst{n}_x"])
+    got = dst1(x)
+    want = x.double() @ sine(n)
+    assert rel(torch.from_numpy(GOLD[f"dst{n}_y"]), want) <= 2 * float(GOLD[f"dst{n}_y__err"]) + 1e-30    # the restatement is the reference's transform
+    err = rel(got, want)
+    print(f"n={n} kernel {err:.3e} reference {float(GOLD[f'dst{n}_y__err']):.3e}")
+    assert err <= 2 * float(GOLD[f"dst{n}_y__err"])
+    assert torch.equal(dst1(x), got)                                 # run to run
+    assert rel(dst1(got), x.double()) <= 4 * float(GOLD[f"dst{n}_y__err"]) + derived(n) * (n == 1)   # involution
+
+
+@pytest.mark.parametrize("n,rows", [(100, 3), (1024, 2)])
+def test_dst1_other_lengths(n, rows):
+    """no golden case: the derived bound.  P = 202 = 2 101 and P = 2050 = 2 5^2 41 take the generic stage"""
+    x = torch.randn(rows, n, generator=torch.Generator().manual_seed(n))
+    err = rel(dst1(x), x.double() @ sine(n))
+    print(f"n={n} kernel {err:.3e} bound {derived(n):.3e}")
+    assert err <= derived(n)
+
+
+@pytest.mark.parametrize("rows", [1, 2, 3, 5, 1025])
+@pytest.mark.parametrize("n", [12, 31])
+def test_dst1_row_counts(n, rows):
+    """the tile is 2 `lines` rows with lines = ceil(rows / 2 / 256) up to what LDS holds: one pair for the small counts (3 is
+    one more than the tile, 5 two tiles and the tail of the pairing), three pairs and an odd row at 1025"""
+    x = torch.randn(rows, n, generator=torch.Generator().manual_seed(rows))
+    got = dst1(x)
+    assert not torch.isnan(got).any()
+    assert rel(got, x.double() @ sine(n)) <= derived(n)
+    # the partner of a row in the complex transform changes its rounding only
+    assert rel(got[:1], dst1(x[:1].clone()).double()) <= 2 * derived(n)
+
+
+def test_dst1_in_place():
+    x = torch.randn(5, 12, generator=torch.Generator().manual_seed(0))
+    want = dst1(x)
+    plan, table = plan_for(12)
+    assert lib().dinv_dst1(E.p(x), E.p(x), 5, 12, ctypes.byref(plan), E.p(table), None) == 0
+    assert torch.equal(x, want)
+
+
+# ---------------------------------------------------------------- StructuredRandom
+def geometry(img, osz, adjoint):
+    if len(img) != 3:
+        return (1, img[-1]), (1, img[-1]), (1, img[-1]), 0, 0, int(np.prod(img[:-1]))
+    C, H, W = img
+    _, Ho, Wo = osz
+    work = (max(H, Ho), max(W, Wo))
+    top, left = math.ceil(abs(H - Ho) / 2), math.ceil(abs(W - Wo) / 2)
+    a, b = ((Ho, Wo), (H, W)) if adjoint else ((H, W), (Ho, Wo))
+    return a, b, work, top, left, C * work[0]
+
+
+def structured(x, diag, img, osz, n_layers, adjoint):
+    (hi, wi), (ho, wo), (hw, ww), top, left, drows = geometry(img, osz, adjoint)
+    L, half = math.floor(n_layers), int(n_layers - math.floor(n_layers) == 0.5)
+    x3 = x.reshape(-1, hi, wi).contiguous()
+    out = torch.full((x3.shape[0], ho, wo), float("nan"))
+    plan, table = plan_for(ww)
+    rc = lib().dinv_structured_apply(E.p(x3), E.p(out), E.p(diag.contiguous()) if L else None, x3.shape[0], hi, wi, ho, wo, hw, ww, top,
+                                     left, drows, L, half, int(adjoint), ctypes.byref(plan), E.p(table), None)
+    assert rc == 0, lib().dinv_last_error()
+    return out.reshape(*x.shape[:-2], ho, wo) if len(img) == 3 else out.reshape(*x.shape[:-1], wo)
+
+
+def pad_to(t, small, big):
+    top, left = math.ceil((big[0] - small[0]) / 2), math.ceil((big[1] - small[1]) / 2)
+    return torch.nn.functional.pad(t, (left, big[1] - small[1] - left, top, big[0] - small[0] - top))
+
+
+def trim_to(t, big, small):
+    top, left = math.ceil((big[0] - small[0]) / 2), math.ceil((big[1] - small[1]) / 2)
+    return t[..., top:top + small[0], left:left + small[1]]
+
+
+def restated(x, diag, img, osz, n_layers, adjoint):
+    """float64: pad, ([F]; D_i, F ...) or its mirror, trim"""
+    x, diag = x.double(), diag.double()
+    L, half = math.floor(n_layers), n_layers - math.floor(n_layers) == 0.5
+    if len(img) == 3:
+        a, b = (osz[1:], img[1:]) if adjoint else (img[1:], osz[1:])
+        work = (max(a[0], b[0]), max(a[1], b[1]))
+        x = pad_to(x, a, work)
+    S = sine(x.shape[-1])
+    if not adjoint:
+        if half:
+            x = x @ S
+        for i in range(L):
+            x = (diag[i] * x) @ S
+    else:
+        for i in range(L):
+            x = diag[L - 1 - i] * (x @ S)
+        if half:
+            x = x @ S
+    return trim_to(x, work, b) if len(img) == 3 else x
+
+
+TAGS = [str(t) for t in GOLD["sr_tags"]]
+
+
+@pytest.mark.parametrize("adjoint", [False, True], ids=["A", "At"])
+@pytest.mark.parametrize("tag", TAGS)
+def test_structured_golden_geometries(tag, adjoint):
+    img, osz = tuple(int(v) for v in GOLD[f"sr_{tag}_img"]), tuple(int(v) for v in GOLD[f"sr_{tag}_out"])
+    nl = float(GOLD[f"sr_{tag}_layers"])
+    diag = torch.from_numpy(GOLD[f"sr_{tag}_diag"])
+    key = f"sr_{tag}_At" if adjoint else f"sr_{tag}_A"
+    x = torch.from_numpy(GOLD[f"sr_{tag}_y" if adjoint else f"sr_{tag}_x"])
+    want = restated(x, diag, img, osz, nl, adjoint)
+    bound = 2 * float(GOLD[key + "__err"])
+    assert rel(torch.from_numpy(GOLD[key]), want) <= bound            # the restatement is the reference's operator
+    got = structured(x, diag, img, osz, nl, adjoint)
+    assert got.shape == want.shape and not torch.isnan(got).any()
+    err = rel(got, want)
+    print(f"{key} kernel {err:.3e} reference {bound / 2:.3e}")
+    assert err <= bound
+    assert torch.equal(got, structured(x, diag, img, osz, nl, adjoint))
+    # rows of a padded result that meet no input row are exactly zero
+    zero = want == 0
+    if len(img) == 3 and got.shape[-2] > x.shape[-2]:
+        assert zero.any() and bool((got[zero].view(torch.int32) & 0x7FFFFFFF == 0).all())
+
+
+def test_structured_adjointness():
+    """<A x, y> = <x, A^T y> holds exactly for the float64 operator, and each kernel is within twice the reference's error e of
+    it, so the two inner products differ by at most e_A |A x| |y| + e_At |x| |A^T y|"""
+    for tag in TAGS:
+        img, osz = tuple(int(v) for v in GOLD[f"sr_{tag}_img"]), tuple(int(v) for v in GOLD[f"sr_{tag}_out"])
+        nl, diag = float(GOLD[f"sr_{tag}_layers"]), torch.from_numpy(GOLD[f"sr_{tag}_diag"])
+        x, y = torch.from_numpy(GOLD[f"sr_{tag}_x"]), torch.from_numpy(GOLD[f"sr_{tag}_y"])
+        Ax, Aty = structured(x, diag, img, osz, nl, False).double(), structured(y, diag, img, osz, nl, True).double()
+        eA, eAt = 2 * float(GOLD[f"sr_{tag}_A__err"]), 2 * float(GOLD[f"sr_{tag}_At__err"])
+        bound = eA * float(Ax.norm() * y.double().norm()) + eAt * float(x.double().norm() * Aty.norm())
+        assert abs(float((Ax * y).sum() - (x * Aty).sum())) <= bound, tag
+
+
+def test_n1024_two_layers():
+    g = torch.Generator().manual_seed(7)
+    diag = torch.where(torch.rand(2, 1024, generator=g) > 0.5, -1.0, 1.0)
+    x = torch.randn(2, 1024, generator=g)
+    for adjoint, key in ((False, "sr_n1024_A__err"), (True, "sr_n1024_At__err")):
+        err = rel(structured(x, diag, (1024,), (1024,), 2, adjoint), restated(x, diag, (1024,), (1024,), 2, adjoint))
+        print(f"n=1024 adjoint={adjoint} kernel {err:.3e} reference {float(GOLD[key]):.3e} derived {derived(1024, 2, 2):.3e}")
+        assert err <= 2 * float(GOLD[key])
+
+
+def test_argument_checks_and_lds_limit():
+    l = lib()
+    assert l.dinv_dst_workspace_bytes(4, 1024) == 0
+    plan, table = plan_for(MAX_N)                 # the largest row: the carve fits (the launch itself is left to the GPU test)
+    x = torch.zeros(2, MAX_N + 1)
+    out = torch.full_like(x, float("nan"))
+    big, big_table = plan_for(MAX_N + 1)
+    assert l.dinv_dst1(E.p(x), E.p(out), 2, MAX_N + 1, ctypes.byref(big), E.p(big_table), None) != 0
+    msg = l.dinv_last_error()
+    assert str(MAX_N).encode() in msg and b"LDS" in msg
+    assert torch.isnan(out).all()                 # no launch happened
+    small = torch.zeros(2, 12)
+    assert l.dinv_dst1(E.p(small), E.p(small), 2, 12, ctypes.byref(plan), E.p(table), None) != 0
+    assert b"plan" in l.dinv_last_error()
+    p12, t12 = plan_for(12)
+    o = torch.empty(2, 8, 12)
+    xx = torch.zeros(2, 8, 12)
+    call = lambda *a: l.dinv_structured_apply(E.p(xx), E.p(o), None, *a, ctypes.byref(p12), E.p(t12), None)
+    assert call(2, 8, 12, 8, 12, 8, 12, 0, 0, 16, 0, 0, 0) != 0 and b"at least one transform" in l.dinv_last_error()
+    assert call(2, 8, 12, 8, 12, 8, 12, 0, 0, 16, 1, 0, 0) != 0 and b"without diagonals" in l.dinv_last_error()
+    assert call(2, 8, 12, 8, 12, 9, 12, 0, 0, 16, 0, 1, 0) != 0 and b"working size" in l.dinv_last_error()
+    assert call(2, 5, 12, 8, 12, 8, 12, 4, 0, 16, 0, 1, 0) != 0 and b"offsets" in l.dinv_last_error()
