@@ -1,10 +1,10 @@
-"""Data-fidelity terms (reference deepinv/optim/data_fidelity.py:26-338, 663-795)."""
+"""Data-fidelity terms (reference deepinv/optim/data_fidelity.py:26-338, 663-795; AmplitudeLoss: 757-773)."""
 from __future__ import annotations
 
 import torch
 
 from ..physics.forward import LinearPhysics
-from .distance import Distance, L1Distance, L2Distance, LogPoissonLikelihoodDistance, PoissonLikelihoodDistance
+from .distance import AmplitudeLossDistance, Distance, L1Distance, L2Distance, LogPoissonLikelihoodDistance, PoissonLikelihoodDistance
 from .potential import Potential
 
 
@@ -92,6 +92,27 @@ class L1(DataFidelity):
             if rel_crit < crit_conv and it > 2:
                 break
         return t
+
+
+class AmplitudeLoss(DataFidelity):
+    r""":math:`\sum_i (\sqrt{|b_i x|^2} - \sqrt{y_i})^2` for :class:`deepinv_amd.physics.PhaseRetrieval` (data_fidelity.py:757-773).
+
+    With :class:`deepinv_amd.physics.RandomPhaseRetrieval` or :class:`deepinv_amd.physics.StructuredRandomPhaseRetrieval` the
+    gradient :math:`2 B^H (Bx \cdot (1 - \sqrt{y / (|Bx|^2 + \epsilon)}))` is two launches: the forward product with the residual
+    factor as its epilogue, and the adjoint.  With any other physics it is the generic ``A_vjp`` route."""
+
+    def __init__(self):
+        super().__init__()
+        self.d = AmplitudeLossDistance()
+
+    def grad(self, x, y, physics, *args, epsilon: float = 1e-12, **kwargs):
+        from ..hip import cdense as hcd
+        from ..physics.phase_retrieval import fused_operator
+
+        B = fused_operator(physics)
+        if B is not None and isinstance(y, torch.Tensor) and y.dtype == torch.float32 and tuple(y.shape) == tuple(B.measurement_shape(x)):
+            return 2 * physics.B_adjoint(B.apply_epilogue(x, hcd.AMPLITUDE, y, epsilon))
+        return super().grad(x, y, physics, *args, epsilon=epsilon, **kwargs)
 
 
 class LogPoissonLikelihood(DataFidelity):

@@ -1,4 +1,4 @@
-"""Distances (reference deepinv/optim/distance.py:13-115, 196-323, 372-395).
+"""Distances (reference deepinv/optim/distance.py:13-115, 196-395).
 
 ``grad`` / ``prox`` of the Poisson, L1 and log-Poisson distances are one launch of dinv_fidelity_pointwise (csrc/elementwise.hip) for
 fp32 tensors on a HIP device; when an input records a gradient, or ``gamma`` is a Tensor, they are the reference's torch expressions, so
@@ -92,6 +92,24 @@ class L1Distance(Distance):
         if ew.fidelity_eligible(u, y, gamma):
             return ew.fidelity_pointwise(ew.FID_L1_PROX, u, y, gamma=gamma)
         return F.softshrink(u - y, lambd=gamma) + y
+
+
+class AmplitudeLossDistance(Distance):
+    r""":math:`\sum_i (\sqrt{u_i} - \sqrt{y_i})^2` for :class:`deepinv_amd.physics.PhaseRetrieval` (distance.py:326-369).  With a
+    phase-retrieval operator of this package the gradient never exists as an array of its own: it is an epilogue of the forward
+    launch (:meth:`deepinv_amd.optim.AmplitudeLoss.grad`)."""
+
+    def __init__(self):
+        super().__init__()
+
+    def fn(self, u, y, *args, **kwargs):
+        # the difference of two roots cancels where the fit is good, and the result is one number per batch entry: the roots, the
+        # difference and the sum are taken in float64 and rounded once, so the loss carries the error of u alone
+        x = torch.sqrt(u.double()) - torch.sqrt(y.double()) if u.dtype == torch.float32 else torch.sqrt(u) - torch.sqrt(y)
+        return (torch.linalg.vector_norm(x, ord=2, dim=tuple(range(1, x.dim()))) ** 2).to(u.dtype)
+
+    def grad(self, u, y, *args, epsilon: float = 1e-12, **kwargs):
+        return 1 - torch.sqrt(y / (u + epsilon))
 
 
 class LogPoissonLikelihoodDistance(Distance):

@@ -1,0 +1,344 @@
+"""Phase retrieval ``y = |Bx|^2`` (reference deepinv/physics/phase_retrieval.py:17-314).  ``B`` is a complex64 linear operator:
+a dense iid Gaussian matrix on csrc/cdense.hip (hip/cdense.py) or a product of 2-D DFTs and unit-modulus diagonals on
+csrc/cstructured.hip (hip/cstructured.py).  With either of them the modulus, the weights of ``A_vjp`` and of the spectral
+initialiser and the residual of the amplitude loss are epilogues of the forward launch, so ``A`` is one launch and ``A_vjp``,
+``AmplitudeLoss.grad`` and one power iteration are two.  With any other ``LinearPhysics`` the methods are the reference's
+expressions.  Ptychography is not part of this module."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from ..hip import cdense as hcd
+from ..hip import cstructured as hcs
+from .forward import LinearPhysics, Physics
+from .structured_random import _changes, compare
+
+
+def _real_like(t, shape) -> bool:
+    return isinstance(t, Tensor) and t.dtype == torch.float32 and tuple(t.shape) == tuple(shape)
+
+
+class _RandomLinear(LinearPhysics):
+    """the linear operator of :class:`RandomPhaseRetrieval`: the reference's ``CompressedSensing(dtype=torch.cfloat)`` with its
+    buffers ``_A``, ``_A_dagger``, ``_A_adjoint`` and ``initial_random_state``.  ``_A_adjoint`` is the view ``_A.conj().T`` and
+    the kernel reads it in place: the device holds one copy of the matrix."""
+
+    def __init__(self, m: int, img_size, channelwise: bool = False, dtype: torch.dtype = torch.cfloat, device="cpu",
+                 rng: torch.Generator = None, **kwargs):
+        super().__init__(device=device, **kwargs)
+        if dtype != torch.cfloat:
+            raise NotImplementedError(f"RandomPhaseRetrieval runs in torch.cfloat on the complex dense kernel, got dtype {dtype}")
+        self.name = f"CS_m{m}"
+        self.img_size = img_size
+        self.channelwise = channelwise
+        self.dtype = dtype
+        self.rng = torch.Generator(device=device) if rng is None else rng
+        self.register_buffer("initial_random_state", self.rng.get_state())
+        n = int(np.prod(img_size[1:])) if channelwise else int(np.prod(img_size))
+        _A = torch.randn((m, n), device=device, dtype=dtype, generator=self.rng) / np.sqrt(m)
+        # once, on the host in complex128: no device solver library is needed
+        _A_dagger = torch.linalg.pinv(_A.detach().cpu().to(torch.complex128)).to(dtype).to(device)
+        self.register_buffer("_A", _A)
+        self.register_buffer("_A_dagger", _A_dagger)
+        self.register_buffer("_A_adjoint", self._A.conj().T)
+        self.to(device=device)
+
+    def _apply(self, fn, *args, **kwargs):
+        # a move of the module handles every buffer on its own: tie _A_adjoint to _A again, so that it stays a view as in the
+        # reference and the device holds one copy of the matrix
+        super()._apply(fn, *args, **kwargs)
+        if "_A" in self._buffers and "_A_adjoint" in self._buffers:
+            self._buffers["_A_adjoint"] = self._buffers["_A"].conj().T
+        return self
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        # the state of a generator of another device type has another size: take it as it is instead of failing on the shape
+        key = prefix + "initial_random_state"
+        if key in state_dict and state_dict[key].shape != self.initial_random_state.shape:
+            self.initial_random_state = state_dict[key].clone().to(self.initial_random_state.device)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        if "_A" in self._buffers:
+            self._buffers["_A_adjoint"] = self._buffers["_A"].conj().T
+
+    def measurement_shape(self, x):
+        N, C = x.shape[:2]
+        return (N, C, self._A.shape[0]) if self.channelwise else (N, self._A.shape[0])
+
+    def apply_epilogue(self, x: Tensor, epilogue: int, aux=None, eps: float = 1e-12) -> Tensor:
+        """``B x`` through an epilogue of hip/cdense.py, in the shape of the measurements"""
+        N, C = x.shape[:2]
+        x = x.reshape(N * C, -1) if self.channelwise else x.reshape(N, -1)
+        if aux is not None:
+            aux = aux.reshape(x.shape[0], -1)
+        y = hcd.apply(x, self._A, epilogue, aux, eps)
+        return y.view(N, C, -1) if self.channelwise else y
+
+    def A(self, x: Tensor, **kwargs) -> Tensor:
+        return self.apply_epilogue(x, hcd.NONE)
+
+    def _back(self, y, M):
+        y = y.type(self.dtype)
+        N = y.shape[0]
+        C, H, W = self.img_size[0], self.img_size[1], self.img_size[2]
+        if self.channelwise:
+            y = y.reshape(N * C, -1)
+        return hcd.apply(y, M).reshape(N, C, H, W)
+
+    def A_adjoint(self, y: Tensor, **kwargs) -> Tensor:
+        return self._back(y, self._A_adjoint)
+
+    def A_dagger(self, y: Tensor, **kwargs) -> Tensor:
+        return self._back(y, self._A_dagger)
+
+
+def generate_diagonal(shape: tuple, mode: str = "uniform_phase", dtype=torch.cfloat, device="cpu"):
+    """a random unit-modulus diagonal, the reference's own draw (structured_random.py:95-98): ``exp(2 pi i u)`` with ``u``
+    uniform, drawn from torch's default generator on the host"""
+    if mode != "uniform_phase":
+        raise ValueError(f"Unsupported mode: {mode}")
+    diag = torch.rand(shape)
+    diag = 2 * np.pi * diag
+    diag = torch.exp(1j * diag)
+    return diag.to(dtype).to(device)
+
+
+class _StructuredLinear(LinearPhysics):
+    """the linear operator of :class:`StructuredRandomPhaseRetrieval`: the reference's ``StructuredRandom`` with the orthonormal
+    ``fft2`` / ``ifft2`` as transforms and complex64 diagonals in the buffer ``diagonals`` ``[L, C, H, W]`` of the working size
+    (the larger of ``img_size`` and ``output_size``).  ``A`` and ``A_adjoint`` are one launch each for any number of layers
+    while the working plane fits the LDS of a workgroup (:func:`deepinv_amd.hip.cstructured.fits`); larger planes take the
+    composed device path, which computes the same."""
+
+    def __init__(self, img_size, output_size, n_layers=1, diagonals=None, device="cpu", **kwargs):
+        super().__init__(device=device, **kwargs)
+        if len(img_size) != 3 or len(output_size) != 3:
+            raise ValueError(f"img_size and output_size must be (C, H, W), got {tuple(img_size)} and {tuple(output_size)}")
+        self.mode = compare(img_size, output_size)
+        self.img_size = img_size
+        self.output_size = output_size
+        self.n_layers = n_layers
+        L = math.floor(n_layers)
+        work = (int(img_size[0]), max(int(img_size[1]), int(output_size[1])), max(int(img_size[2]), int(output_size[2])))
+        if diagonals is None:
+            raise ValueError("the diagonals are required: a tensor [layers, C, H, W] of the working size, or a list of its layers")
+        if isinstance(diagonals, (list, tuple)):
+            diagonals = torch.stack(list(diagonals), dim=0) if len(diagonals) else torch.zeros((0, *work), dtype=torch.cfloat, device=device)
+        if diagonals.dtype != torch.cfloat:
+            raise TypeError(f"the diagonals must be complex64, got {diagonals.dtype}; convert them with .to(torch.cfloat)")
+        if diagonals.shape[0] < L or tuple(diagonals.shape[1:]) != work:
+            raise ValueError(f"the diagonals must have shape [{L}, {', '.join(map(str, work))}] (the working size: the larger of "
+                             f"img_size and output_size), got {tuple(diagonals.shape)}")
+        self.register_buffer("diagonals", diagonals)
+        self.to(device)
+
+    def _geometry(self, adjoint):
+        C, H, W = (int(s) for s in self.img_size)
+        _, Ho, Wo = (int(s) for s in self.output_size)
+        top, _, left, _ = _changes(self.img_size, self.output_size)
+        work = (max(H, Ho), max(W, Wo))
+        a, b = ((Ho, Wo), (H, W)) if adjoint else ((H, W), (Ho, Wo))
+        return a, b, work, top, left, C
+
+    def measurement_shape(self, x):
+        return (*x.shape[:-2], int(self.output_size[1]), int(self.output_size[2]))
+
+    def _run(self, x, adjoint, epilogue=hcd.NONE, aux=None, eps=1e-12):
+        L = math.floor(self.n_layers)
+        half = self.n_layers - L == 0.5
+        geom = self._geometry(adjoint)
+        (h_in, w_in), (h_out, w_out) = geom[0], geom[1]
+        if x.dim() < 3 or tuple(x.shape[-2:]) != (h_in, w_in) or x.shape[-3] != self.img_size[0]:
+            raise ValueError(f"expected an input [..., {self.img_size[0]}, {h_in}, {w_in}], got shape {tuple(x.shape)}")
+        lead = x.shape[:-2]
+        if aux is not None:
+            aux = aux.reshape(-1, h_out, w_out)
+        out = hcs.apply(x.reshape(-1, h_in, w_in), self.diagonals[:L], geom, L, half, adjoint, epilogue, aux, eps)
+        return out.reshape(*lead, h_out, w_out)
+
+    def apply_epilogue(self, x: Tensor, epilogue: int, aux=None, eps: float = 1e-12) -> Tensor:
+        """``B x`` through an epilogue of hip/cstructured.py, in the shape of the measurements"""
+        return self._run(x, False, epilogue, aux, eps)
+
+    def A(self, x: Tensor, *args, **kwargs) -> Tensor:
+        return self._run(x, False)
+
+    def A_adjoint(self, y: Tensor, *args, **kwargs) -> Tensor:
+        return self._run(y.type(torch.cfloat), True)
+
+
+def fused_operator(physics):
+    """the linear operator of a phase-retrieval physics when its epilogues are kernels, else None"""
+    B = getattr(physics, "B", None)
+    return B if isinstance(B, (_RandomLinear, _StructuredLinear)) else None
+
+
+class PhaseRetrieval(Physics):
+    r"""
+    :math:`A(x) = |Bx|^2` with :math:`B` a :class:`deepinv_amd.physics.LinearPhysics` (phase_retrieval.py:17-104).
+
+    :param deepinv_amd.physics.LinearPhysics B: the linear forward operator.
+    """
+
+    def __init__(self, B: LinearPhysics, **kwargs):
+        super().__init__(**kwargs)
+        self.name = "Phase Retrieval"
+        self.B = B
+
+    def A(self, x: Tensor, **kwargs) -> Tensor:
+        B = fused_operator(self)
+        if B is not None:
+            return B.apply_epilogue(x, hcd.ABS2)
+        return self.B(x, **kwargs).abs().square()
+
+    def A_dagger(self, y: Tensor, **kwargs) -> Tensor:
+        """an initial reconstruction by the spectral method (:func:`deepinv_amd.optim.phase_retrieval.spectral_methods`)"""
+        from ..optim.phase_retrieval import spectral_methods
+
+        return spectral_methods(y, self, **kwargs)
+
+    def A_adjoint(self, y: Tensor, **kwargs) -> Tensor:
+        return self.B_adjoint(y, **kwargs)
+
+    def B_adjoint(self, y: Tensor, **kwargs) -> Tensor:
+        return self.B.A_adjoint(y, **kwargs)
+
+    def B_dagger(self, y):
+        """the linear pseudo-inverse of :math:`B`"""
+        return self.B.A_dagger(y)
+
+    def forward(self, x, **kwargs):
+        return self.sensor(self.noise(self.A(x, **kwargs)))
+
+    def A_vjp(self, x, v):
+        r""":math:`2 \overline{B}^{\top} \text{diag}(Bx) v`"""
+        B = fused_operator(self)
+        if B is not None and _real_like(v, B.measurement_shape(x)):
+            return 2 * self.B_adjoint(B.apply_epilogue(x, hcd.WEIGHT, v))
+        return 2 * self.B_adjoint(self.B(x) * v)
+
+    def release_memory(self):
+        del self.B
+        torch.cuda.empty_cache()
+        return
+
+
+class RandomPhaseRetrieval(PhaseRetrieval):
+    r"""
+    Random phase retrieval with :math:`B_{i,j} \sim \mathcal{N}(0, \frac{1}{2m}) + \mathrm{i} \mathcal{N}(0, \frac{1}{2m})`
+    (phase_retrieval.py:107-180).  Same signature, buffers and state-dict keys (``B._A``, ``B._A_adjoint``, ``B._A_dagger``,
+    ``B.initial_random_state``, ``initial_random_state``) as the reference, so ``load_state_dict`` of a reference state dict
+    works.  The matrix is the reference's own draw; the pseudo-inverse is computed once at construction, on the host in
+    complex128, and rounded to complex64.  ``dtype`` other than ``torch.cfloat`` raises ``NotImplementedError``.
+
+    :param int m: number of measurements.
+    :param tuple img_size: shape (C, H, W) of inputs.
+    :param bool channelwise: channels are processed independently with the same matrix.
+    :param torch.dtype dtype: ``torch.cfloat``.
+    :param str device: device of the matrix.
+    :param torch.Generator rng: generator of the matrix, on ``device``.
+    """
+
+    def __init__(self, m, img_size, channelwise=False, dtype=torch.cfloat, device="cpu", rng: torch.Generator = None, **kwargs):
+        self.m = m
+        self.img_size = img_size
+        self.channelwise = channelwise
+        self.dtype = dtype
+        if rng is None:
+            self.rng = torch.Generator(device=device)
+        else:
+            if torch.device(rng.device).type != torch.device(device).type or (
+                    torch.device(device).index is not None and rng.device.index is not None
+                    and rng.device.index != torch.device(device).index):
+                raise ValueError("The random generator is not on the same device as the Physics Generator. Got random generator on "
+                                 f"{rng.device} and the Physics Generator on {device}.")
+            self.rng = rng
+        B = _RandomLinear(m=m, img_size=img_size, channelwise=channelwise, dtype=dtype, device=device, rng=self.rng)
+        super().__init__(B, **kwargs)
+        self.register_buffer("initial_random_state", self.rng.get_state())
+        self.name = "Random Phase Retrieval"
+        self.to(device)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        key = prefix + "initial_random_state"
+        if key in state_dict and state_dict[key].shape != self.initial_random_state.shape:
+            self.initial_random_state = state_dict[key].clone().to(self.initial_random_state.device)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def get_A_squared_mean(self):
+        return self.B._A.var() + self.B._A.mean() ** 2
+
+
+class StructuredRandomPhaseRetrieval(PhaseRetrieval):
+    r"""
+    :math:`A(x) = |\prod_{i=1}^N (F D_i) x|^2` with :math:`F` the orthonormal 2-D DFT and :math:`D_i` diagonals of unit modulus
+    and uniform random phase; ``n_layers = N + 0.5`` applies one more :math:`F` first (phase_retrieval.py:183-314).  Oversampling
+    zero-pads the input to the output shape, undersampling trims the output, both centred.  Same signature as the reference;
+    the state-dict key is ``B.diagonals``.  One launch per ``A`` / ``B`` / ``B_adjoint`` for any ``n_layers`` while the working
+    plane fits the LDS of a workgroup (:func:`deepinv_amd.hip.cstructured.fits`), the composed device path above that.
+
+    :param tuple img_size: shape (C, H, W) of inputs.
+    :param tuple output_size: shape (C, H, W) of outputs.
+    :param float n_layers: number of layers :math:`N`, or :math:`N + 0.5`.
+    :param str transform: ``"fft"``.
+    :param str diagonal_mode: ``"uniform_phase"``.
+    :param bool shared_weights: the same diagonal in every layer.
+    :param torch.dtype dtype: ``torch.cfloat``.
+    :param str device: device of the physics.
+    """
+
+    def __init__(self, img_size: tuple, output_size: tuple, n_layers: int, transform="fft", diagonal_mode="uniform_phase",
+                 shared_weights=False, dtype=torch.cfloat, device="cpu", **kwargs):
+        if dtype != torch.cfloat:
+            raise NotImplementedError(f"StructuredRandomPhaseRetrieval runs in torch.cfloat on the fused FFT-layer kernel, got dtype {dtype}")
+        if transform != "fft":
+            raise ValueError(f"Unimplemented transform: {transform}")
+        if not (n_layers % 1 == 0.5 or n_layers % 1 == 0):
+            raise ValueError("n_layers must be an integer or an integer plus 0.5")
+        if n_layers < 0.5:
+            raise ValueError("n_layers must be at least 0.5: the operator needs one transform")
+        if output_size is None:
+            output_size = img_size
+        self.img_size = img_size
+        self.output_size = output_size
+        self.n = torch.prod(torch.tensor(self.img_size))
+        self.m = torch.prod(torch.tensor(self.output_size))
+        self.oversampling_ratio = self.m / self.n
+        self.n_layers = n_layers
+        self.structure = self.get_structure(self.n_layers)
+        self.shared_weights = shared_weights
+        self.dtype = dtype
+        self.mode = compare(img_size, output_size)
+        shape = tuple(self.output_size) if self.mode == "oversampling" else tuple(self.img_size)
+        L = math.floor(self.n_layers)
+        if not shared_weights:
+            diagonals = [generate_diagonal(shape, diagonal_mode, self.dtype, device) for _ in range(L)]
+        else:
+            diagonals = [generate_diagonal(shape, diagonal_mode, self.dtype, device)] * L
+        B = _StructuredLinear(img_size=self.img_size, output_size=self.output_size, n_layers=self.n_layers, diagonals=diagonals,
+                              device=device)
+        super().__init__(B, **kwargs)
+        self.name = "Structured Random Phase Retrieval"
+        self.to(device)
+
+    @property
+    def diagonals(self):
+        """the list of diagonals, one per layer: views of the buffer ``B.diagonals``"""
+        return [self.B.diagonals[i] for i in range(math.floor(self.n_layers))]
+
+    def B_dagger(self, y):
+        return self.B.A_adjoint(y)
+
+    def get_A_squared_mean(self):
+        if self.n_layers == 0.5:
+            print("warning: computing the mean of the squared operator for a single Fourier transform.")
+            return None
+        return self.diagonals[0].var() + self.diagonals[0].mean() ** 2
+
+    @staticmethod
+    def get_structure(n_layers) -> str:
+        """the structure of the operator as a string, e.g. ``"FDFD"``"""
+        return "FD" * math.floor(n_layers) + "F" * (n_layers % 1 == 0.5)

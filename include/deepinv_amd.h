@@ -35,7 +35,7 @@ typedef void* dinv_stream_t; /* hipStream_t */
 /* library / error                                                            */
 /* ------------------------------------------------------------------------- */
 const char* dinv_last_error(void);
-int dinv_version(void);   /* 15 = this header (adds the DST-I / StructuredRandom entry points dinv_dst1, dinv_structured_apply and the dense fp32 product dinv_dense_apply); 14: (adds dinv_poisson_noise and dinv_fidelity_pointwise); 13: (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
+int dinv_version(void);   /* 16 = this header (adds the complex64 phase-retrieval entry points dinv_cdense_apply and dinv_cstructured_apply); 15: (adds the DST-I / StructuredRandom entry points dinv_dst1, dinv_structured_apply and the dense fp32 product dinv_dense_apply); 14: (adds dinv_poisson_noise and dinv_fidelity_pointwise); 13: (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
 /* number of visible HIP devices (0 when no GPU): used by the host to fail loudly */
 int dinv_device_count(int* count);
 
@@ -757,6 +757,49 @@ int dinv_structured_apply(const float* x, float* out, const float* diag, int64_t
 size_t dinv_dense_workspace_bytes(int64_t I, int64_t K, int64_t R);
 int dinv_dense_apply(const float* in, const float* M, float* out, int64_t I, int64_t K, int64_t R, int64_t ldm,
                      int32_t transposed, void* workspace, size_t workspace_bytes, dinv_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
+/* Phase retrieval, y = |Bx|^2 (deepinv/physics/phase_retrieval.py:17-314; optim/distance.py:326-369;                     */
+/* optim/phase_retrieval.py:106-193)                                                                                        */
+/* ------------------------------------------------------------------------- */
+/* complex64 only, as interleaved fp32 pairs.  Both products end in a pointwise epilogue on the finished complex value z:
+ *     DINV_CDENSE_NONE       out = z                                   complex output
+ *     DINV_CDENSE_ABS2       out = |z|^2                               REAL output of the same shape
+ *     DINV_CDENSE_WEIGHT     out = z * aux                             aux real, of the output's shape
+ *     DINV_CDENSE_AMPLITUDE  out = z * (1 - sqrt(aux / (|z|^2 + eps))) aux real (the measurements y)
+ * aux is read only by the last two and may be null otherwise.
+ *
+ * dinv_cdense_apply: out[i, r] = sum_k in[i, k] op(M)(r, k) with op(M)(r, k) = M[r, k] (transposed = 0, M is [R, K]) or M[k, r]
+ * (transposed = 1, M is [K, R]), conjugated when conj = 1; ldm is the row stride of M in complex elements.  Four fp32 MFMAs per
+ * complex multiply-accumulate, fp32 accumulation.  Any I, K, R.  K is split over workgroups and the partial sums are added in slice
+ * order from `workspace` (dinv_cdense_workspace_bytes(I, K, R) bytes; 0 means none is needed and null is accepted): no atomics,
+ * bit-reproducible.  out must not alias in or aux.
+ *
+ * dinv_cstructured_apply: the whole of B = prod_i (F D_i) [F] (adjoint = 0) or of its adjoint (adjoint = 1) as ONE launch for any
+ * number of layers, F the orthonormal 2-D DFT of a plane.  x is [planes, H_in, W_in], out [planes, H_out, W_out], the working size
+ * (H_work, W_work) is the larger of the two and the smaller side sits at rows top .., columns left .. of it (the reference's
+ * centred pad / trim: ceil of half the difference).
+ *     B          [F if half]  then  F D_i  for i = 0 .. layers - 1
+ *     B^H        conj(D_{layers-1-i}) F^-1  for i = 0 .. layers - 1,  then  [F^-1 if half]
+ * `diag` is [layers, diag_planes, H_work, W_work] complex; plane p uses diagonal plane p % diag_planes (diag_planes = C for a
+ * [C, H, W] image shared by the batch).  A workgroup holds a whole working plane in LDS through all layers, so the plane must
+ * fit: dinv_cstructured_fits(H_work, W_work) != 0 (two buffers and the tables of both axes within 160 KB); the call
+ * returns an error otherwise.  plan_w / table_w come from dinv_fft_plan_init(W_work), plan_h / table_h from
+ * dinv_fft_plan_init(H_work) (the tables on the device).  layers + half >= 1.  x must not alias out. */
+#define DINV_CDENSE_NONE 0
+#define DINV_CDENSE_ABS2 1
+#define DINV_CDENSE_WEIGHT 2
+#define DINV_CDENSE_AMPLITUDE 3
+size_t dinv_cdense_workspace_bytes(int64_t I, int64_t K, int64_t R);
+int dinv_cdense_apply(const float* in, const float* M, float* out, const float* aux, int64_t I, int64_t K, int64_t R, int64_t ldm,
+                      int32_t transposed, int32_t conj, int32_t epilogue, float eps, void* workspace, size_t workspace_bytes,
+                      dinv_stream_t stream);
+int dinv_cstructured_fits(int32_t H_work, int32_t W_work);
+int dinv_cstructured_apply(const float* x, float* out, const float* diag, const float* aux, int64_t planes, int32_t H_in,
+                           int32_t W_in, int32_t H_out, int32_t W_out, int32_t H_work, int32_t W_work, int32_t top, int32_t left,
+                           int64_t diag_planes, int32_t layers, int32_t half, int32_t adjoint, int32_t epilogue, float eps,
+                           const dinv_fft_plan* plan_w, const void* table_w_dev, const dinv_fft_plan* plan_h,
+                           const void* table_h_dev, dinv_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,289 @@
+"""Phase retrieval on the host emulation of the kernels: deepinv_amd/csrc/cdense.hip and cstructured.hip (with fft.hip for the
+plans and the composed path) built for the host by tests/emu/Makefile as a library of their own, and the product's Python layer
+pointed at it, so the public classes run on CPU tensors with the real kernel code underneath.  The cases and their bounds are
+those of tests/phase_retrieval_cases.py; the kernel-level cases here go to the C entry points directly."""
+import contextlib
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import phase_retrieval_cases as PC
+from phase_retrieval_cases import C128, GOLD, U, crel, up
+
+import deepinv_amd as dinv
+import deepinv_amd.hip as H
+from deepinv_amd.hip import cdense as hcd
+from deepinv_amd.hip import cstructured as hcs
+from deepinv_amd.hip import fft as hfft
+
+EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
+TARGET = "libdeepinv_amd_emu_phase_retrieval.so"
+DEV = torch.device("cpu")
+
+
+@contextlib.contextmanager
+def emu_phase_retrieval():
+    """hip/cdense.py, hip/cstructured.py and hip/fft.py on the emulated library: TEST INFRASTRUCTURE, as tests/emu_backend.py"""
+    subprocess.run(["make", "-C", EMU_DIR, "-j4", "SRCS=fft cdense cstructured", f"TARGET={TARGET}"], check=True, stdout=subprocess.DEVNULL)
+    emu = H._DeviceGuardedLib(ctypes.CDLL(os.path.join(EMU_DIR, TARGET)))
+    emu.dinv_last_error.restype = ctypes.c_char_p
+    emu.dinv_fft_table_bytes.restype = ctypes.c_size_t
+    emu.dinv_fft_table_bytes.argtypes = [ctypes.c_int32]
+    emu.dinv_fft_plan_init.argtypes = [ctypes.c_int32, ctypes.POINTER(H.FftPlan), ctypes.c_void_p]
+    emu.dinv_fft_c2c_axis.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(H.FftPlan),
+                                      ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p]
+    mods = [H, hcd, hcs, hfft]
+    patches = {"lib": lambda: emu, "require_hip": lambda *t: None, "stream_ptr": lambda device: ctypes.c_void_p(0)}
+    saved = [(m, n, getattr(m, n)) for m in mods for n in patches if hasattr(m, n)]
+    for m, n, _ in saved:
+        setattr(m, n, patches[n])
+    saved.append((H, "_lib", H._lib))
+    H._lib = emu
+    hcd._declared = hcs._declared = False
+    cache = dict(H._plan_cache)
+    H._plan_cache.clear()
+    cur = torch.cuda.current_device
+    torch.cuda.current_device = lambda: 0
+    try:
+        yield emu
+    finally:
+        torch.cuda.current_device = cur
+        for m, n, v in saved:
+            setattr(m, n, v)
+        hcd._declared = hcs._declared = False
+        H._plan_cache.clear()
+        H._plan_cache.update(cache)
+
+
+@pytest.fixture(autouse=True, scope="module")
+def _emu():
+    with emu_phase_retrieval() as emu:
+        yield emu
+
+
+# ---------------------------------------------------------------- the dense kernel
+def slices(I, K, R):
+    return max(hcd._l().dinv_cdense_workspace_bytes(I, K, R) // (8 * I * R), 1)
+
+
+def within_gamma(got, x, M, S):
+    """|z - exact| <= sqrt(2) gamma_{2K+S} sum_k |x_k| |m_k| elementwise: the real part is a sum of 2 K products accumulated by
+    fused multiply-adds in S slices, |xr||mr| + |xi||mi| <= |x||m|, and the same holds for the imaginary part (Higham, Accuracy
+    and Stability of Numerical Algorithms, section 3.1)"""
+    n = 2 * x.shape[1] + S
+    gamma = n * U / (1 - n * U)
+    x, M = up(x), up(M)
+    return bool(((up(got) - x @ M.t()).abs() <= math_sqrt2 * gamma * (x.abs() @ M.abs().t())).all())
+
+
+math_sqrt2 = 2.0 ** 0.5
+
+
+def crandn(*shape, seed=0):
+    return torch.randn(*shape, dtype=torch.complex64, generator=torch.Generator().manual_seed(seed))
+
+
+@pytest.mark.parametrize("form", ["rows", "transposed", "conj", "adjoint"])
+@pytest.mark.parametrize("I,K,R", [(1, 9, 6), (3, 192, 48), (33, 100, 40), (70, 65, 33), (2, 1000, 48)])
+def test_cdense_forms_and_shapes(I, K, R, form):
+    """every op(M) without a copy of M; I = 33 and 70 take the two wider accumulator forms with a ragged last tile, K = 192 and
+    1000 several slices (1000 ends its last slice short), K = 9 a single slice that stores the result itself"""
+    x, base = crandn(I, K, seed=I + K), crandn(R, K, seed=R)
+    if form == "rows":
+        M = base
+    elif form == "transposed":
+        M = base.t().contiguous().t()
+    elif form == "conj":
+        M = base.conj()
+    else:
+        M = base.conj().t().contiguous().mH        # the view _A.conj().T of a [K, R] matrix
+    store, ldm, tr, cj = hcd._matrix(M)
+    assert (tr, cj) == {"rows": (0, 0), "transposed": (1, 0), "conj": (0, 1), "adjoint": (1, 1)}[form]
+    assert store.data_ptr() == M.data_ptr()
+    got = hcd.apply(x, M)
+    assert within_gamma(got, x, M.resolve_conj(), slices(I, K, R))
+    assert torch.equal(got, hcd.apply(x, M))                       # bit-reproducible
+    if K in (192, 1000):
+        assert slices(I, K, R) > 1
+
+
+def test_cdense_split_k_exact():
+    """ones make every partial sum exact, so a k counted twice or dropped shows as an integer error"""
+    for K in (1000, 97, 65, 16, 17):
+        x, M = torch.full((2, K), 1 + 1j, dtype=torch.complex64), torch.full((40, K), 1 - 2j, dtype=torch.complex64)
+        want = torch.full((2, 40), K * (1 + 1j) * (1 - 2j), dtype=torch.complex64)
+        assert torch.equal(hcd.apply(x, M), want), K
+        assert torch.equal(hcd.apply(x, M.conj()), torch.full((2, 40), K * (1 + 1j) * (1 + 2j), dtype=torch.complex64)), K
+
+
+def test_cdense_copies_only_what_it_must():
+    M = crandn(12, 20)
+    assert hcd._matrix(M[:, ::2])[0].data_ptr() != M.data_ptr()    # a column stride: one contiguous copy
+    store, ldm, tr, cj = hcd._matrix(M[:, :7])                      # a matrix inside a wider one: read in place
+    assert store.data_ptr() == M.data_ptr() and (ldm, tr, cj) == (20, 0, 0)
+    x = crandn(3, 7, seed=1)
+    assert within_gamma(hcd.apply(x, M[:, :7]), x, M[:, :7], 1)
+    assert within_gamma(hcd.apply(x, M[:, ::2][:, :7]), x, M[:, ::2][:, :7], 1)
+
+
+def test_cdense_argument_checks(_emu):
+    x, M, out = torch.zeros(2, 8, dtype=torch.complex64), torch.zeros(4, 8, dtype=torch.complex64), torch.zeros(2, 4, dtype=torch.complex64)
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    call = lambda ldm, ep, aux, K=8: hcd._l().dinv_cdense_apply(p(x), p(M), p(out), p(aux), 2, K, 4, ldm, 0, 0, ep, 0.0, None, 0, None)
+    assert call(7, 0, None) != 0 and b"row stride" in _emu.dinv_last_error()
+    assert call(8, 2, None) != 0 and b"needs a real array" in _emu.dinv_last_error()
+    assert call(8, 7, None) != 0 and b"epilogue" in _emu.dinv_last_error()
+    assert call(8, 0, None, K=0) != 0 and b"bad shape" in _emu.dinv_last_error()
+    with pytest.raises(TypeError, match=r"\.to\(torch\.cfloat\)"):
+        hcd.apply(torch.zeros(2, 8), M)
+    with pytest.raises(TypeError, match=r"\.to\(torch\.cfloat\)"):
+        hcd.apply(x, M.to(C128))
+    with pytest.raises(TypeError, match="real fp32"):
+        hcd.apply(x, M, hcd.WEIGHT, torch.zeros(2, 4, dtype=torch.complex64))
+
+
+# ---------------------------------------------------------------- the public classes on golden cases
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("tag", PC.RP_TAGS)
+def test_random_golden(tag, B):
+    p, r = PC.random_physics(tag, DEV)
+    PC.run_operators(f"{tag}_b{B}", p, r, DEV)
+
+
+def test_random_docstring_example():
+    p, r = PC.random_physics("doc", DEV)
+    y = p(PC.gold("doc_x"))
+    assert torch.allclose(y, PC.gold("doc_expected"), atol=1e-4), y
+    PC.check(y, "doc_y", r.A(up(PC.gold("doc_x"))))
+
+
+@pytest.mark.parametrize("tag", PC.SP_TAGS)
+def test_structured_golden(tag):
+    p, r = PC.structured_physics(tag, DEV)
+    x, X, _, _ = PC.run_operators(f"sp_{tag}", p, r, DEV)
+    if f"sp_{tag}_unitary" in GOLD:
+        e = crel(p.B_adjoint(p.B(x)), X)
+        print(f"unitarity {e:.3e} reference {float(GOLD[f'sp_{tag}_unitary']):.3e}")
+        assert e <= 2 * float(GOLD[f"sp_{tag}_unitary"])
+    assert torch.equal(p.B(x), p.B(x))
+
+
+@pytest.mark.parametrize("tag", ["rp48", "rp20cw"])
+def test_random_epilogues_autograd_dot(tag):
+    p, r = PC.random_physics(tag, DEV)
+    key = f"{tag}_b3"
+    x = PC.gold(f"{key}_x")
+    PC.run_epilogues(p, r, x, float(GOLD[f"{key}_B__err"]), DEV)
+    PC.run_autograd(key, p, r, DEV)
+    assert PC.cdot(p.B, x, PC.gold(f"{key}_yc")) <= 1e-5
+
+
+def test_random_epilogue_zero_row():
+    """an output element with z = 0 and y > 0: the factor is huge and finite, the product exactly zero"""
+    M = crandn(10, 12)
+    M[3] = 0
+    x, y = crandn(2, 12, seed=1), torch.rand(2, 10, generator=torch.Generator().manual_seed(2)) + 0.5
+    got = hcd.apply(x, M, hcd.AMPLITUDE, y, 1e-12)
+    assert torch.isfinite(got.real).all() and bool((got[:, 3] == 0).all())
+
+
+@pytest.mark.parametrize("tag", ["eq1.5", "under2.5", "over1", "odd2"])
+def test_structured_epilogues_autograd_dot(tag):
+    p, r = PC.structured_physics(tag, DEV)
+    key = f"sp_{tag}"
+    x = PC.gold(f"{key}_x").clone()
+    PC.run_autograd(key, p, r, DEV)
+    assert PC.cdot(p.B, x, PC.gold(f"{key}_yc")) <= 1e-5
+    x[1] = 0                                                        # a whole plane with z = 0
+    got, Z, y = PC.run_epilogues(p, r, x, float(GOLD[f"{key}_B__err"]), DEV)
+    assert bool((got[1] == 0).all()) and bool((Z[1] == 0).all())
+
+
+@pytest.mark.parametrize("batch", [33, 70])
+def test_random_wide_batches(batch):
+    """the wider accumulator forms through the public class, against complex128 einsum"""
+    p, r = PC.random_physics("rp48", DEV)
+    x = crandn(batch, 3, 8, 8, seed=batch)
+    got = p.B(x)
+    assert within_gamma(got, x.reshape(batch, -1), p.B._A, slices(batch, 192, 48))
+    # |z|^2 of the same sum z: B rounds each part of z once (its |z|^2 moves by at most 2 u), A squares the unrounded sum in
+    # double and rounds once (u)
+    assert crel(p.A(x), up(got).abs().square()) <= 3 * U
+
+
+def test_spectral_random():
+    p = dinv.physics.RandomPhaseRetrieval(m=400, img_size=(1, 8, 8))
+    p.B._A.copy_(PC.gold("spec_rand_A"))
+    r = PC.restate_random(p.B._A, p.B._A_dagger, (1, 8, 8), False)
+    PC.run_spectral("spec_rand", p, r, DEV)
+    # early stop: the golden script chose rtol clear of the criterion by 1.5 on both sides, so the count cannot differ
+    y, x0 = PC.gold("spec_rand_y"), PC.gold("spec_rand_x0")
+    lamb, rtol, stop = float(GOLD["early_lamb"]), float(GOLD["early_rtol"]), int(GOLD["early_stop_iter"])
+    got = dinv.optim.spectral_methods(y, p, x=x0, n_iter=int(GOLD["spec_iters"]), lamb=lamb, early_stop=True, rtol=rtol)
+    PC.check(got, "early_x", r.spectral(up(y), up(x0), int(GOLD["spec_iters"]), lamb, rtol))
+    assert torch.equal(got, dinv.optim.spectral_methods(y, p, x=x0, n_iter=stop, lamb=lamb, early_stop=False))
+    # log, and the initial guess drawn when x is None
+    est, metrics = dinv.optim.spectral_methods(y, p, x=x0, n_iter=3, x_true=x0, log=True, early_stop=False)
+    assert len(metrics) == 3 and est.shape == x0.shape
+    torch.manual_seed(5)
+    a = dinv.optim.spectral_methods(y, p, n_iter=2)
+    torch.manual_seed(5)
+    assert torch.equal(a, dinv.optim.spectral_methods(y, p, x=torch.randn_like(x0), n_iter=2))
+    assert set(dinv.optim.spectral_methods_wrapper(y, p, n_iter=2, x=x0)) == {"est"}
+
+
+def test_spectral_structured():
+    p = dinv.physics.StructuredRandomPhaseRetrieval((1, 16, 16), (1, 23, 23), 2)
+    diag = PC.gold("spec_struct_diag")
+    p.load_state_dict({"B.diagonals": diag})
+    PC.run_spectral("spec_struct", p, PC.restate_structured(diag, (1, 16, 16), (1, 23, 23), 2), DEV)
+
+
+def test_structured_lds_boundary():
+    """the largest square plane of the fused kernel and the next one up, which takes the composed path: both against
+    complex128 torch.fft within the derived bound"""
+    n = PC.largest_fused_square()
+    assert hcs.fits(n, n) and not hcs.fits(n + 1, n + 1) and 90 <= n <= 110
+    for side in (n, n + 1):
+        img = (1, side, side)
+        p = dinv.physics.StructuredRandomPhaseRetrieval(img, img, 1)
+        x = crandn(1, *img, seed=side)
+        r = PC.restate_structured(p.B.diagonals, img, img, 1)
+        bound = PC.derived_fft_bound(side, side, 1, 1, DEV)
+        e, et = crel(p.B(x), r.B(up(x))), crel(p.B_adjoint(x), r.Bt(up(x)))
+        print(f"{side} x {side}: B {e:.3e} B^H {et:.3e} bound {bound:.3e}")
+        assert e <= bound and et <= bound
+        assert crel(p.A(x), r.A(up(x))) <= 2 * bound + U
+
+
+def test_cstructured_argument_checks(_emu):
+    n = PC.largest_fused_square()
+    x = torch.zeros(1, n + 1, n + 1, dtype=torch.complex64)
+    with pytest.raises(RuntimeError, match="LDS"):
+        hcs._CStructured.apply(x, None, ((n + 1, n + 1), (n + 1, n + 1), (n + 1, n + 1), 0, 0, 1), 0, 1, False, 0, None, 0.0)
+    with pytest.raises(TypeError, match=r"\.to\(torch\.cfloat\)"):
+        hcs.apply(torch.zeros(1, 8, 12), None, ((8, 12), (8, 12), (8, 12), 0, 0, 1), 0, 1, False)
+    with pytest.raises(ValueError, match="at least one transform"):
+        hcs.apply(torch.zeros(1, 8, 12, dtype=torch.complex64), None, ((8, 12), (8, 12), (8, 12), 0, 0, 1), 0, 0, False)
+
+
+def test_generic_physics_takes_the_reference_expressions():
+    """a PhaseRetrieval over any other LinearPhysics: no epilogue kernels, the reference's expressions.  These are complex64
+    torch expressions over 12 terms, a few u = 6e-8 each, checked loosely: the test is about the route, not the rounding"""
+    M = crandn(7, 12)
+    B = dinv.physics.LinearPhysics(A=lambda x, **kw: x.reshape(x.shape[0], -1) @ M.t(),
+                                   A_adjoint=lambda y, **kw: (y.to(torch.complex64) @ M.conj()).reshape(-1, 1, 3, 4))
+    p = dinv.physics.PhaseRetrieval(B)
+    x, v = crandn(2, 1, 3, 4, seed=1), torch.randn(2, 7, generator=torch.Generator().manual_seed(2))
+    Z = up(x).reshape(2, -1) @ up(M).t()
+    assert crel(p.A(x), Z.abs().square()) <= 1e-6
+    assert crel(p.A_vjp(x, v), 2 * ((Z * up(v)) @ up(M).conj()).reshape(2, 1, 3, 4)) <= 1e-6
+    y = p.A(crandn(2, 1, 3, 4, seed=3))
+    g = dinv.optim.AmplitudeLoss().grad(x, y, p)
+    want = 2 * ((Z * (1 - torch.sqrt(up(y) / (Z.abs().square() + 1e-12)))) @ up(M).conj()).reshape(2, 1, 3, 4)
+    assert crel(g, want) <= 1e-5
+    assert dinv.optim.spectral_methods(y, p, x=x, n_iter=2).shape == x.shape
