@@ -19,7 +19,6 @@
 // A plane fits when that is within kMaxLdsBytes (dinv_cstructured_fits).
 #include "fft_core.hpp"
 
-#include <atomic>
 #include <cmath>
 
 using namespace dinv;
@@ -43,17 +42,12 @@ struct CStructArgs {
                            // a bias common to every output, which an iteration over the operator accumulates coherently
 };
 
-size_t table_bytes(int n) {
-    size_t b = (size_t)n * 8 + (((size_t)n * 4 + 15) / 16) * 16;
-    return ((b + 15) / 16) * 16;
-}
-
 size_t buf_elems(int H, int W) {
     const size_t a = (size_t)H * fft_line_stride(W), b = (size_t)W * fft_line_stride(H);
     return a > b ? a : b;
 }
 
-size_t lds_bytes(int H, int W) { return table_bytes(W) + table_bytes(H) + 2 * buf_elems(H, W) * sizeof(float2); }
+size_t lds_bytes(int H, int W) { return fft_table_lds_bytes(W) + fft_table_lds_bytes(H) + 2 * buf_elems(H, W) * sizeof(float2); }
 
 // diagonal applied before / after 2-D transform t of T = layers + half (-1: none).  A: [F] then (D_i, F) for i = 0 .. L - 1;
 // A_adjoint: (F^-1, conj D_{L-1-i}) for i = 0 .. L - 1, then [F^-1]
@@ -66,7 +60,7 @@ template <bool INV>
 __device__ __forceinline__ void run_layers(const CStructArgs& a, const dinv_fft_plan& pw, const dinv_fft_plan& ph, float2* cur, float2* oth,
                                            const float2* tww, const int* permw, const float2* twh, const int* permh,
                                            const float2* dplane, int64_t dstride, int64_t plane, int tid) {
-    const int H = a.H, W = a.W, LSW = (W % 2 == 0) ? W + 1 : W, LSH = (H % 2 == 0) ? H + 1 : H;
+    const int H = a.H, W = a.W, LSW = fft_line_stride(W), LSH = fft_line_stride(H);
     const int T = a.layers + a.half, total = H * W;
     for (int t = 0; t < T; ++t) {
         // rows: H lines of length W
@@ -113,15 +107,16 @@ __device__ __forceinline__ void run_layers(const CStructArgs& a, const dinv_fft_
 __global__ __launch_bounds__(kThreads) void cstructured_plane_kernel(CStructArgs a, dinv_fft_plan pw, dinv_fft_plan ph, const void* table_w,
                                                                      const void* table_h) {
     DINV_DYN_LDS(unsigned char, smem);
-    const int H = a.H, W = a.W, LSW = (W % 2 == 0) ? W + 1 : W;
+    const int H = a.H, W = a.W, LSW = fft_line_stride(W);
     const int tid = threadIdx.x;
-    const size_t tbw = (size_t)W * 8 + (((size_t)W * 4 + 15) / 16) * 16, tbw16 = ((tbw + 15) / 16) * 16;
-    const size_t tbh = (size_t)H * 8 + (((size_t)H * 4 + 15) / 16) * 16, tbh16 = ((tbh + 15) / 16) * 16;
-    float2* tww = reinterpret_cast<float2*>(smem);
-    int* permw = reinterpret_cast<int*>(smem + (size_t)W * 8);
-    float2* twh = reinterpret_cast<float2*>(smem + tbw16);
-    int* permh = reinterpret_cast<int*>(smem + tbw16 + (size_t)H * 8);
-    float2* cur = reinterpret_cast<float2*>(smem + tbw16 + tbh16);
+    // [tables of W][tables of H][cur][oth]
+    const LdsCarve Tw = carve_lds(smem, W, 0, 0, false);
+    const LdsCarve Th = carve_lds(reinterpret_cast<unsigned char*>(Tw.buf), H, 0, 0, false);
+    float2* tww = Tw.tw;
+    int* permw = Tw.perm;
+    float2* twh = Th.tw;
+    int* permh = Th.perm;
+    float2* cur = Th.buf;
     float2* oth = cur + a.buf_elems;
     load_tables(tww, permw, table_w, W, tid, kThreads);
     load_tables(twh, permh, table_h, H, tid, kThreads);
@@ -196,17 +191,8 @@ extern "C" int dinv_cstructured_apply(const float* x, float* out, const float* d
     a.scale = (float)sc;
     a.scale_lo = (float)(sc - (double)a.scale);
     const size_t lds = lds_bytes(H_work, W_work);
-    if (lds > 48 * 1024) {
-        static std::atomic<bool> raised[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        if (!raised[dev & 63].load(std::memory_order_relaxed)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cstructured_plane_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes);
-            if (e != hipSuccess) return fail(100 + (int)e, "hipFuncSetAttribute(lds=%zu): %s", kMaxLdsBytes, hipGetErrorString(e));
-            raised[dev & 63].store(true, std::memory_order_relaxed);
-        }
-    }
+    if (lds > kDefaultLdsBytes)
+        if (int e = raise_lds_cap<cstructured_plane_kernel>(kMaxLdsBytes)) return e;
     hipLaunchKernelGGL(cstructured_plane_kernel, dim3((unsigned)planes), dim3(kThreads), lds, (hipStream_t)stream, a, *plan_w, *plan_h,
                        table_w, table_h);
     DINV_CHECK_LAUNCH();

@@ -135,7 +135,6 @@ void split_k(int64_t I, int64_t K, int64_t R, int64_t* S, int64_t* kchunk) {
     *S = ceil_div(K, c);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 

@@ -1,7 +1,6 @@
 // Shared helpers of the DRUNet convolution kernels (drunet.hip, drunet_wino.hip).
 #pragma once
 #include "common.hpp"
-#include <atomic>
 
 namespace dinv_drunet {
 
@@ -124,16 +123,9 @@ inline FastDiv make_fastdiv(uint32_t d) {
 }
 
 // compute units per XCD of the current device (32 on MI355X: 256 CUs in 8 XCDs)
-inline int cus_per_xcd(int dev) {
-    static std::atomic<int> cache[64];
-    int v = cache[dev & 63].load(std::memory_order_relaxed);
-    if (v == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-        v = n / 8;
-        cache[dev & 63].store(v, std::memory_order_relaxed);
-    }
-    return v;
+inline int cus_per_xcd() {
+    const int n = dinv::compute_units();
+    return (n < 8 ? 256 : n) / 8;
 }
 
 inline int check_geom(const dinv_act_geom* g) {

@@ -292,15 +292,14 @@ template <bool IN_SPLIT, bool OUT_SPLIT, bool RELU, int NRES, int TC, int NREP>
 int launch_s2(S2Args a, hipStream_t st) {
     using T = Tile2<TC, NREP>;
     constexpr size_t lds = (size_t)T::LDS_UNITS * sizeof(uint4);
-    static_assert(2 * lds <= 160 * 1024, "two workgroups must fit one CU");
+    static_assert(2 * lds <= kMaxLdsBytes, "two workgroups must fit one CU");
     const int ntr = (int)ceil_div(a.rows, T::TR);
     a.ntc = (int)ceil_div(a.g.w, TC);
     a.ntiles = ntr * a.ntc;
     a.tiles_per_xcd = (int32_t)ceil_div(a.ntiles, 8);
     const dim3 grid((unsigned)(a.tiles_per_xcd * a.ytiles * 8)), block(256);
-    auto kern = conv3x3_split2d_kernel<IN_SPLIT, OUT_SPLIT, RELU, NRES, TC, NREP>;
-    hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e_ != hipSuccess) return fail(100 + (int)e_, "hipFuncSetAttribute: %s", hipGetErrorString(e_));
+    constexpr auto kern = conv3x3_split2d_kernel<IN_SPLIT, OUT_SPLIT, RELU, NRES, TC, NREP>;
+    if (int e = raise_lds_cap<kern>(lds)) return e;
     hipLaunchKernelGGL(kern, grid, block, lds, st, a);
     DINV_CHECK_LAUNCH();
     return 0;

@@ -28,7 +28,6 @@
 //   wave xr finishes A^T s for channel sub-block xr: fused ReLU / residual add, float4 stores of interior
 //   pixels only.
 #include "drunet_common.hpp"
-#include <atomic>
 #include <type_traits>
 
 using namespace dinv;
@@ -489,18 +488,11 @@ int launch_shape(WinoArgs a, int tiles_y, int tiles_x, hipStream_t st) {
     a.d_img = make_fastdiv((uint32_t)(a.nty * a.ntx));
     a.d_ntx = make_fastdiv((uint32_t)a.ntx);
     a.d_nct = make_fastdiv((uint32_t)a.nct);
-    const size_t shm = S::LDSF * sizeof(float);
-    static std::atomic<uint64_t> configured{0};   // per instantiation: bit d = attribute set on device d
-    auto kern = conv3x3_wino_kernel<TH, TW, RELU, NRES>;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(3, "hipGetDevice failed");
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(configured.load(std::memory_order_relaxed) & bit)) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-            return fail(3, "hipFuncSetAttribute(max dynamic LDS) failed");
-        configured.fetch_or(bit, std::memory_order_relaxed);
-    }
-    const int cpx = cus_per_xcd(dev);
+    constexpr size_t shm = S::LDSF * sizeof(float);
+    static_assert(shm <= kMaxLdsBytes, "the tile must fit one CU");
+    constexpr auto kern = conv3x3_wino_kernel<TH, TW, RELU, NRES>;
+    if (int e = raise_lds_cap<kern>(shm)) return e;
+    const int cpx = cus_per_xcd();
     a.slots = (int32_t)(a.per_xcd < cpx ? a.per_xcd : cpx);
     hipLaunchKernelGGL(kern, dim3((unsigned)(a.slots * 8)), dim3(NTHR), shm, st, a);
     DINV_CHECK_LAUNCH();

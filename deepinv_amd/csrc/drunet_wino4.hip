@@ -734,18 +734,11 @@ int launch_shape(W4Args a, hipStream_t st) {
     a.d_img = make_fastdiv((uint32_t)(a.nty * a.ntx));
     a.d_ntx = make_fastdiv((uint32_t)a.ntx);
     a.d_nct = make_fastdiv((uint32_t)a.nct);
-    const size_t shm = S::LDSF * sizeof(float) + 16;   // + the ticket word of the tail split
-    static std::atomic<uint64_t> configured{0};   // per instantiation: bit d = attribute set on device d
-    auto kern = conv3x3_wino4_kernel<TH, TW, RELU, NRES, false, BF3, BIAS>;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(3, "hipGetDevice failed");
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(configured.load(std::memory_order_relaxed) & bit)) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-            return fail(3, "hipFuncSetAttribute(max dynamic LDS) failed");
-        configured.fetch_or(bit, std::memory_order_relaxed);
-    }
-    const int cpx = cus_per_xcd(dev);
+    constexpr size_t shm = S::LDSF * sizeof(float) + 16;   // + the ticket word of the tail split
+    static_assert(shm <= kMaxLdsBytes, "the tile must fit one CU");
+    constexpr auto kern = conv3x3_wino4_kernel<TH, TW, RELU, NRES, false, BF3, BIAS>;
+    if (int e = raise_lds_cap<kern>(shm)) return e;
+    const int cpx = cus_per_xcd();
     DINV_REQUIRE(cpx <= 64, "winograd F(4,3) conv: the ticket area of the tail split holds 64 tiles per XCD (device has %d CUs per XCD)", cpx);
     // whole rounds of cpx tiles per XCD, then the tail: cut along the input channels when a workspace was given
     const int64_t ntail = a.per_xcd % cpx;
@@ -762,13 +755,8 @@ int launch_shape(W4Args a, hipStream_t st) {
         DINV_CHECK_LAUNCH();
     }
     if (a.split_f > 1) {
-        auto kern_s = conv3x3_wino4_kernel<TH, TW, RELU, NRES, true, BF3, BIAS>;
-        static std::atomic<uint64_t> configured_s{0};
-        if (!(configured_s.load(std::memory_order_relaxed) & bit)) {
-            if (hipFuncSetAttribute((const void*)kern_s, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-                return fail(3, "hipFuncSetAttribute(max dynamic LDS) failed");
-            configured_s.fetch_or(bit, std::memory_order_relaxed);
-        }
+        constexpr auto kern_s = conv3x3_wino4_kernel<TH, TW, RELU, NRES, true, BF3, BIAS>;
+        if (int e = raise_lds_cap<kern_s>(shm)) return e;
         a.slots = (int32_t)(a.ntail * a.split_f);
         hipLaunchKernelGGL(kern_s, dim3((unsigned)(a.slots * 8)), dim3(NTHR), shm, st, a);
     }
@@ -804,9 +792,7 @@ extern "C" void dinv_debug_wino4_timing(long long* p) { g_w4_dbg = p; }
 // workspace of the tail split: per XCD one ticket word and up to (compute units per XCD) part buffers of 64 couts x 512 pixels
 static size_t w4_ws_tickets() { return 8 * 64 * sizeof(int32_t); }
 extern "C" size_t dinv_conv3x3_winograd4_workspace_bytes(void) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    return w4_ws_tickets() + (size_t)8 * cus_per_xcd(dev) * 8192 * 16;
+    return w4_ws_tickets() + (size_t)8 * cus_per_xcd() * 8192 * 16;
 }
 
 extern "C" int dinv_conv3x3_winograd4_last_split(int32_t* split_f, int32_t* n_tail_tiles) {

@@ -23,7 +23,6 @@
 // HBM traffic: x once, the diagonals once, y once.  No atomics, fixed order: bit-reproducible.
 #include "fft_core.hpp"
 
-#include <atomic>
 #include <cmath>
 
 using namespace dinv;
@@ -87,7 +86,7 @@ __device__ __forceinline__ void put_odd(float2* __restrict__ base, const int* __
 
 __global__ __launch_bounds__(kThreads) void dst_tile_kernel(DstArgs a, dinv_fft_plan plan, const void* table) {
     DINV_DYN_LDS(unsigned char, smem);
-    const int n = a.n, P = plan.n, LS = (P % 2 == 0) ? P + 1 : P;
+    const int n = a.n, P = plan.n, LS = fft_line_stride(P);
     const int tid = threadIdx.x;
     LdsCarve L = carve_lds(smem, P, a.lines, LS, true);
     load_tables(L.tw, L.perm, table, P, tid, kThreads);
@@ -172,12 +171,8 @@ __global__ __launch_bounds__(kThreads) void dst_tile_kernel(DstArgs a, dinv_fft_
     }
 }
 
-size_t carve_bytes(int P, int lines) {
-    const int LS = fft_line_stride(P);
-    size_t b = (size_t)P * 8 + (((size_t)P * 4 + 15) / 16) * 16;
-    b = ((b + 15) / 16) * 16;
-    return b + (size_t)2 * lines * LS * 8;
-}
+// the tables and both line buffers: the kernel always carves for a generic stage
+size_t carve_bytes(int P, int lines) { return fft_lds_bytes(P, lines, true); }
 
 int launch(DstArgs a, const dinv_fft_plan* plan, const void* table, hipStream_t s) {
     DINV_REQUIRE(plan && table, "dst: null plan / table");
@@ -202,17 +197,8 @@ int launch(DstArgs a, const dinv_fft_plan* plan, const void* table, hipStream_t 
     if (blocks < 1) blocks = 1;      // zero rows only
     DINV_REQUIRE(blocks < ((int64_t)1 << 31), "dst: too many rows");
     const size_t lds = carve_bytes(P, lines);
-    if (lds > 48 * 1024) {
-        static std::atomic<bool> raised[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        if (!raised[dev & 63].load(std::memory_order_relaxed)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dst_tile_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes);
-            if (e != hipSuccess) return fail(100 + (int)e, "hipFuncSetAttribute(lds=%zu): %s", kMaxLdsBytes, hipGetErrorString(e));
-            raised[dev & 63].store(true, std::memory_order_relaxed);
-        }
-    }
+    if (lds > kDefaultLdsBytes)
+        if (int e = raise_lds_cap<dst_tile_kernel>(kMaxLdsBytes)) return e;
     hipLaunchKernelGGL(dst_tile_kernel, dim3((unsigned)blocks), dim3(kThreads), lds, s, a, *plan, table);
     DINV_CHECK_LAUNCH();
     return 0;

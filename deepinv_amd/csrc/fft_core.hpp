@@ -239,16 +239,18 @@ DINV_HD void load_tables(float2* tw_s, int* perm_s, const void* table, int N, in
 }
 
 // LDS line stride: odd (in float2 units) so that column tiles scatter conflict-free.
-inline int fft_line_stride(int n) { return (n % 2 == 0) ? n + 1 : n; }
+DINV_HD int fft_line_stride(int n) { return (n % 2 == 0) ? n + 1 : n; }
 
-// LDS carve: [tw N*8][perm N*4 rounded to 8][buf lines*LS*8][alt lines*LS*8 if generic]
-inline size_t fft_lds_bytes(const dinv_fft_plan& p, int lines) {
-    const int LS = fft_line_stride(p.n);
-    size_t b = (size_t)p.n * 8 + (((size_t)p.n * 4 + 15) / 16) * 16;
-    b = ((b + 15) / 16) * 16;
-    b += (size_t)lines * LS * 8 * (p.generic ? 2 : 1);
-    return b;
+DINV_HD size_t round_up16(size_t b) { return ((b + 15) / 16) * 16; }
+
+// The tables of one length in LDS: [tw n*8][perm n*4], padded so that what follows is 16-byte aligned.
+DINV_HD size_t fft_table_lds_bytes(int n) { return round_up16((size_t)n * 8 + round_up16((size_t)n * 4)); }
+
+// LDS carve of a tile: [tables][buf lines*LS*8][alt lines*LS*8 if generic]
+inline size_t fft_lds_bytes(int n, int lines, bool generic) {
+    return fft_table_lds_bytes(n) + (size_t)lines * fft_line_stride(n) * 8 * (generic ? 2 : 1);
 }
+inline size_t fft_lds_bytes(const dinv_fft_plan& p, int lines) { return fft_lds_bytes(p.n, lines, p.generic != 0); }
 
 struct LdsCarve {
     float2* tw;
@@ -257,17 +259,14 @@ struct LdsCarve {
     float2* alt;
 };
 
+// (lines = 0 carves the tables alone: buf is then the first byte after them)
 DINV_HD LdsCarve carve_lds(unsigned char* smem, int N, int lines, int LS, bool generic) {
     LdsCarve c;
     c.tw = reinterpret_cast<float2*>(smem);
     c.perm = reinterpret_cast<int*>(smem + (size_t)N * 8);
-    size_t off = (size_t)N * 8 + (((size_t)N * 4 + 15) / 16) * 16;
-    off = ((off + 15) / 16) * 16;
-    c.buf = reinterpret_cast<float2*>(smem + off);
+    c.buf = reinterpret_cast<float2*>(smem + fft_table_lds_bytes(N));
     c.alt = generic ? c.buf + (size_t)lines * LS : c.buf;
     return c;
 }
-
-constexpr size_t kMaxLdsBytes = 160 * 1024;
 
 }  // namespace dinv

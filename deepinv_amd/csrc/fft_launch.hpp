@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void fft_rows_kernel(Io io, int64_t nlines, in
                                                        const void* table, int centered, float scale) {
     DINV_DYN_LDS(unsigned char, smem);
     const int N = plan.n;
-    const int LS = (N % 2 == 0) ? N + 1 : N;
+    const int LS = fft_line_stride(N);
     const int tid = threadIdx.x;
     LdsCarve L = carve_lds(smem, N, lpb, LS, plan.generic != 0);
     load_tables(L.tw, L.perm, table, N, tid, 256);
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void fft_cols_kernel(Io io, int64_t Q, int tq,
                                                        float scale) {
     DINV_DYN_LDS(unsigned char, smem);
     const int N = plan.n;
-    const int LS = (N % 2 == 0) ? N + 1 : N;
+    const int LS = fft_line_stride(N);
     const int tid = threadIdx.x;
     LdsCarve L = carve_lds(smem, N, tq, LS, plan.generic != 0);
     load_tables(L.tw, L.perm, table, N, tid, 256);
@@ -162,16 +162,6 @@ inline int cols_tile_width(const dinv_fft_plan& p, int64_t Q) {
     return tq;
 }
 
-template <class K>
-inline int set_lds_limit(K kernel, size_t bytes) {
-    if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return fail(100 + (int)e, "hipFuncSetAttribute(lds=%zu): %s", bytes, hipGetErrorString(e));
-    }
-    return 0;
-}
-
 // ------------------------------------------------------------------ static-plan dispatch
 constexpr int kMaxGrid = 256 * 8;
 #ifndef DINV_WAVE_WPB
@@ -207,9 +197,7 @@ inline int launch_rows_static_L(Io io, int64_t nlines, const void* table, int in
                 constexpr bool PF = DINV_WAVE_PREFETCH != 0;
                 if (io.wave_rows_ok(LW, nlines)) {
                     const int64_t wtiles = ceil_div(nlines, LW);
-                    int cus = 256;
-                    { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount; }
-                    const int64_t resident = (int64_t)cus * (4 * MINW / WPB);          // workgroups the chip holds at MINW waves per SIMD
+                    const int64_t resident = (int64_t)compute_units() * (4 * MINW / WPB);          // workgroups the chip holds at MINW waves per SIMD
                     const unsigned wgrid = (unsigned)std::min<int64_t>(ceil_div(wtiles, WPB), resident);
                     if (inverse)
                         hipLaunchKernelGGL((fft_rows_wave_kernel<P, Io, true, LW, WPB, MINW, PF>), dim3(wgrid), dim3(64 * WPB), 0, s, io,
@@ -287,11 +275,11 @@ inline int launch_rows(Io io, int64_t nlines, const dinv_fft_plan& plan, const v
     const int64_t blocks = ceil_div(nlines, lpb);
     DINV_REQUIRE(blocks < (1ll << 31), "too many fft lines (%lld)", (long long)nlines);
     if (inverse) {
-        if (int e = set_lds_limit(fft_rows_kernel<Io, true>, lds)) return e;
+        if (lds > kDefaultLdsBytes) if (int e = raise_lds_cap<fft_rows_kernel<Io, true>>(kMaxLdsBytes)) return e;
         hipLaunchKernelGGL((fft_rows_kernel<Io, true>), dim3((unsigned)blocks), dim3(256), lds, s, io, nlines, lpb,
                            plan, table, centered, scale);
     } else {
-        if (int e = set_lds_limit(fft_rows_kernel<Io, false>, lds)) return e;
+        if (lds > kDefaultLdsBytes) if (int e = raise_lds_cap<fft_rows_kernel<Io, false>>(kMaxLdsBytes)) return e;
         hipLaunchKernelGGL((fft_rows_kernel<Io, false>), dim3((unsigned)blocks), dim3(256), lds, s, io, nlines,
                            lpb, plan, table, centered, scale);
     }
@@ -317,11 +305,11 @@ inline int launch_cols(Io io, int64_t P, int64_t Q, const dinv_fft_plan& plan, c
     const int64_t blocks = P * qtiles;
     DINV_REQUIRE(blocks < (1ll << 31), "too many fft tiles (%lld)", (long long)blocks);
     if (inverse) {
-        if (int e = set_lds_limit(fft_cols_kernel<Io, true>, lds)) return e;
+        if (lds > kDefaultLdsBytes) if (int e = raise_lds_cap<fft_cols_kernel<Io, true>>(kMaxLdsBytes)) return e;
         hipLaunchKernelGGL((fft_cols_kernel<Io, true>), dim3((unsigned)blocks), dim3(256), lds, s, io, Q, tq,
                            qtiles, plan, table, centered, scale);
     } else {
-        if (int e = set_lds_limit(fft_cols_kernel<Io, false>, lds)) return e;
+        if (lds > kDefaultLdsBytes) if (int e = raise_lds_cap<fft_cols_kernel<Io, false>>(kMaxLdsBytes)) return e;
         hipLaunchKernelGGL((fft_cols_kernel<Io, false>), dim3((unsigned)blocks), dim3(256), lds, s, io, Q, tq,
                            qtiles, plan, table, centered, scale);
     }

@@ -27,7 +27,6 @@
 // Plain adds and subtracts in a fixed order: no atomics, bit-reproducible.
 #include "common.hpp"
 
-#include <atomic>
 #include <cmath>
 
 using namespace dinv;
@@ -185,37 +184,12 @@ int ilog2(int64_t v) {
     return l;
 }
 bool pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// compute units of the current device (256 on MI355X), cached per device
-int compute_units() {
-    static std::atomic<int> cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    int v = cache[dev & 63].load(std::memory_order_relaxed);
-    if (v == 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) v = 256;
-        cache[dev & 63].store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
 
 int launch(const Pass& p, int64_t tiles, const float* x, const float* y, const float* mask, float* out, hipStream_t s) {
     DINV_REQUIRE(tiles > 0 && tiles < ((int64_t)1 << 31), "hadamard: too many tiles");
     const size_t lds = lds_bytes(p.nt);
-    if (lds > 48 * 1024) {
-        // tiles above the default dynamic-LDS limit: raise the kernel's limit to the largest tile, once per device
-        static std::atomic<bool> raised[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        if (!raised[dev & 63].load(std::memory_order_relaxed)) {
-            const size_t top = lds_bytes(1 << kTileLog2);
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(hadamard_tile_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)top);
-            if (e != hipSuccess) return fail(100 + (int)e, "hipFuncSetAttribute(lds=%zu): %s", top, hipGetErrorString(e));
-            raised[dev & 63].store(true, std::memory_order_relaxed);
-        }
-    }
+    if (lds > kDefaultLdsBytes)      // the cap: the largest tile
+        if (int e = raise_lds_cap<hadamard_tile_kernel>(lds_bytes(1 << kTileLog2))) return e;
     int threads = p.nt / 16;
     threads = threads < 64 ? 64 : (threads > kMaxThreads ? kMaxThreads : threads);
     hipLaunchKernelGGL(hadamard_tile_kernel, dim3((unsigned)tiles), dim3(threads), lds, s, p, x, y, mask, out);

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void mri_rows_combine_kernel(const float2* __r
                                                                int centered, float scale) {
     DINV_DYN_LDS(unsigned char, smem);
     const int N = plan.n;
-    const int LS = (N % 2 == 0) ? N + 1 : N;
+    const int LS = fft_line_stride(N);
     const int tid = threadIdx.x;
     LdsCarve L = carve_lds(smem, N, lpb, LS, plan.generic != 0);
     float2* acc = (plan.generic ? L.alt : L.buf) + (size_t)lpb * LS;
@@ -954,7 +954,8 @@ extern "C" int dinv_mri_adjoint(const dinv_mri_desc* d, const float* y, const fl
         DINV_CHECK_LAUNCH();
         return 0;
     }
-    if (int e = set_lds_limit(mri_rows_combine_kernel, lds)) return e;
+    if (lds > kDefaultLdsBytes)
+        if (int e = raise_lds_cap<mri_rows_combine_kernel>(kMaxLdsBytes)) return e;
     const int64_t nlines = (int64_t)d->batch * R;
     const int64_t blocks = ceil_div(nlines, lpb);
     hipLaunchKernelGGL(mri_rows_combine_kernel, dim3((unsigned)blocks), dim3(256), lds, s, t, mp, x, nlines, R, d->coils,

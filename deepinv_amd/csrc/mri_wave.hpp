@@ -569,9 +569,7 @@ inline bool wave2d_ok(const dinv_mri_desc* d, int op) {
 }
 
 inline int resident_waves_grid(int64_t wave_tiles, int wpb) {
-    int cus = 256, dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount;
+    const int cus = compute_units();
     const int64_t resident = std::max<int64_t>((int64_t)cus * 4 * DINV_MRIW_MINW / wpb, cus);       // DINV_MRIW_MINW waves per SIMD
     return (int)std::min<int64_t>(ceil_div(wave_tiles, wpb), resident);
 }
@@ -583,7 +581,7 @@ template <class P, int R>
 constexpr int rows_wpb() {
     using TF = TileFft<P, false, true, R, 64>;
     constexpr size_t per_wave = ((TF::lds_floats2 + 1) / 2 * 2) * sizeof(float2), tab = TF::TAB * sizeof(float2);
-    return per_wave * DINV_MRIW_WPB + tab <= 160 * 1024 ? DINV_MRIW_WPB : 4;
+    return per_wave * DINV_MRIW_WPB + tab <= kMaxLdsBytes ? DINV_MRIW_WPB : 4;
 }
 
 template <int R, bool YIN>

@@ -622,16 +622,6 @@ constexpr int kSlackFloats = 4096;   // tail of the packed image: windows may ru
         default: { constexpr int NB = 1; STMT; } break;              \
     }
 
-template <class K>
-int set_dyn_lds(K kernel, size_t bytes) {
-    if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return fail(100 + (int)e, "hipFuncSetAttribute(lds=%zu): %s", bytes, hipGetErrorString(e));
-    }
-    return 0;
-}
-
 }  // namespace
 
 #if DINV_RADON_PART != 1
@@ -771,8 +761,10 @@ extern "C" size_t dinv_radon_tiled_workspace_bytes(const dinv_radon_desc* d, int
 #if DINV_RADON_PART != 2
 #define DINV_FWD_LAUNCH(PF)                                                                                              \
     do {                                                                                                                 \
-        if (int e = set_dyn_lds(radon_fwd_tiled_kernel<NB, false, PF>, lds)) return e;                                  \
-        if (int e = set_dyn_lds(radon_fwd_tiled_kernel<NB, true, PF>, lds)) return e;                                   \
+        if (lds > kDefaultLdsBytes) {                                                                                    \
+            if (int e = raise_lds_cap<radon_fwd_tiled_kernel<NB, false, PF>>(kMaxLdsBytes)) return e;                    \
+            if (int e = raise_lds_cap<radon_fwd_tiled_kernel<NB, true, PF>>(kMaxLdsBytes)) return e;                     \
+        }                                                                                                                \
         if (plan->n_chunks_plain > 0)                                                                                    \
             hipLaunchKernelGGL((radon_fwd_tiled_kernel<NB, false, PF>), dim3(g.njb, plan->n_chunks_plain, g.groups),    \
                                dim3(64 * kw), lds, s, g, (const float*)xp, xn, cs2, blob + L.off_angles,                \
@@ -842,7 +834,9 @@ extern "C" int dinv_radon_adjoint_tiled(const dinv_radon_desc* d, const float* s
         float* sp = reinterpret_cast<float*>(ws);
         const size_t lds = ((size_t)((g.G + 3) & ~3) + (size_t)KA * JW * NB) * sizeof(float) + KA * sizeof(float2) +
                            KA * sizeof(int);
-        if (int e = set_dyn_lds(radon_adj_tiled_kernel<NB>, lds)) return e;
+        DINV_REQUIRE(lds <= kMaxLdsBytes, "grid of %d does not fit the LDS tile of the tiled adjoint", g.G);
+        if (lds > kDefaultLdsBytes)
+            if (int e = raise_lds_cap<radon_adj_tiled_kernel<NB>>(kMaxLdsBytes)) return e;
         hipLaunchKernelGGL(radon_pack_sino2<NB>, dim3(pk_blocks), dim3(256), 0, s, g, sino, sp);
         hipLaunchKernelGGL(radon_adj_tiled_kernel<NB>, dim3((g.W + 15) / 16, (g.W + 15) / 16, g.groups), dim3(256), lds, s,
                            g, (const float*)sp, xn, cs2, norm_dev, x);
@@ -903,7 +897,8 @@ extern "C" int dinv_radon_ramp_fft(int32_t n_img, int32_t n_det, int32_t n_angle
     while (CT > 1 && ((size_t)P + (size_t)CT * (P + 1)) * sizeof(float2) > kMaxLdsBytes) CT >>= 1;
     const size_t lds = ((size_t)P + (size_t)CT * (P + 1)) * sizeof(float2);
     DINV_REQUIRE(lds <= kMaxLdsBytes, "detector axis too long for the in-LDS ramp filter (%d)", n_det);
-    if (int e = set_dyn_lds(ramp_fft_kernel, lds)) return e;
+    if (lds > kDefaultLdsBytes)
+        if (int e = raise_lds_cap<ramp_fft_kernel>(kMaxLdsBytes)) return e;
     const int ncol = (n_angles + 1) / 2;
     hipLaunchKernelGGL(ramp_fft_kernel, dim3((ncol + CT - 1) / CT, n_img), dim3(256), lds,
                        reinterpret_cast<hipStream_t>(stream), n_img, n_det, n_angles, P, CT, *plan, fft_table_dev,

@@ -267,7 +267,6 @@ int make_geo(int32_t nd, int64_t planes, int32_t D, int32_t H, int32_t W, Geo& g
     return 0;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <vector>
 #include <typeinfo>
 
@@ -54,16 +55,42 @@ struct dim3 {
 typedef struct emu_stream_* hipStream_t;
 typedef int hipError_t;
 constexpr hipError_t hipSuccess = 0;
-inline hipError_t hipGetLastError() { return hipSuccess; }
-inline const char* hipGetErrorString(hipError_t) { return "emulated"; }
+constexpr hipError_t hipErrorInvalidValue = 1;
 inline hipError_t hipGetDeviceCount(int* c) { *c = 0; return hipSuccess; }
 inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
-constexpr int hipFuncAttributeMaxDynamicSharedMemorySize = 0;
-inline hipError_t hipFuncSetAttribute(const void*, int, int) { return hipSuccess; }
-struct hipDeviceProp_t { int multiProcessorCount = 256; };
 constexpr int hipDeviceAttributeMultiprocessorCount = 0;
 inline hipError_t hipDeviceGetAttribute(int* v, int, int) { *v = 16; return hipSuccess; }   // 2 "CUs" per XCD: short tile lists per workgroup
-inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { *p = hipDeviceProp_t(); return hipSuccess; }
+
+// The dynamic-LDS opt-in, enforced as the runtime does: hipFuncSetAttribute records a kernel's cap by its address (one registry
+// for all translation units of a library), and a launch that asks for more than the runtime's default limit and more than its
+// kernel's cap does not run: it leaves an error for hipGetLastError, so a launch path that forgot its opt-in fails in the CPU
+// suite.  The limit is the runtime's own, 64 KB: up to there a launch needs no attribute (the gather Radon kernels and the tiled
+// convolutions of blur.hip launch that much without one); the launchers that do opt in start at the stricter
+// dinv::kDefaultLdsBytes, which the attribute-call counter below lets a test observe.
+namespace emu {
+constexpr size_t kDefaultDynLds = 64 * 1024;
+struct LdsCaps {
+    std::map<const void*, size_t> cap;
+    int attribute_calls = 0;
+    bool refused = false;       // a launch was refused and hipGetLastError has not read it yet
+};
+inline LdsCaps lds_caps;
+}  // namespace emu
+constexpr int hipFuncAttributeMaxDynamicSharedMemorySize = 0;
+inline hipError_t hipFuncSetAttribute(const void* f, int, int bytes) {
+    ++emu::lds_caps.attribute_calls;
+    emu::lds_caps.cap[f] = (size_t)bytes;
+    return hipSuccess;
+}
+inline hipError_t hipGetLastError() {
+    const bool refused = emu::lds_caps.refused;
+    emu::lds_caps.refused = false;
+    return refused ? hipErrorInvalidValue : hipSuccess;
+}
+inline const char* hipGetErrorString(hipError_t e) {
+    return e == hipSuccess ? "emulated" : "emulated: dynamic LDS above the default limit and above the kernel's cap (hipFuncSetAttribute)";
+}
+extern "C" __attribute__((used)) inline int dinv_emu_func_attribute_calls() { return emu::lds_caps.attribute_calls; }
 
 // ------------------------------------------------------------------ the fiber scheduler
 namespace emu {
@@ -164,6 +191,15 @@ inline void run_block(const std::function<void()>& body, dim3 block) {
 }
 template <class K, class... Args>
 inline void launch(K kernel, dim3 grid, dim3 block, size_t shmem, Args... args) {
+    if (shmem > kDefaultDynLds) {
+        const auto it = lds_caps.cap.find(reinterpret_cast<const void*>(kernel));
+        if (it == lds_caps.cap.end() || shmem > it->second) {
+            lds_caps.refused = true;
+            fprintf(stderr, "hip_emu: launch with %zu B of dynamic LDS, the kernel's cap is %zu B\n", shmem,
+                    it == lds_caps.cap.end() ? kDefaultDynLds : it->second);
+            return;
+        }
+    }
     gridDim = grid;
     blockDim = block;
     if (g.dynsmem.size() < shmem + 64) g.dynsmem.resize(shmem + 64);
