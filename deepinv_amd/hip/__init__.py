@@ -65,7 +65,7 @@ def _declare(lib):
     lib.dinv_mri_workspace_bytes.argtypes = [ctypes.POINTER(MriDesc)]
     for name in ("dinv_mri_forward", "dinv_mri_adjoint"):
         getattr(lib, name).argtypes = [ctypes.POINTER(MriDesc), vp, vp, vp, vp, vp, sz, vp]
-    # optional symbol groups are declared by the modules that own them (radon, conv, drunet)
+    # the other symbol groups are declared by the modules that own them, each in its _declare(lib)
 
 
 _tls = threading.local()
@@ -79,6 +79,7 @@ class _DeviceGuardedLib:
     def __init__(self, cdll):
         object.__setattr__(self, "_cdll", cdll)
         object.__setattr__(self, "_wrapped", {})
+        object.__setattr__(self, "_declares", set())      # the _declare functions applied so far (declare_once)
 
     def __getattr__(self, name):
         w = self._wrapped.get(name)
@@ -108,6 +109,14 @@ class _DeviceGuardedLib:
         return w
 
 
+def declare_once(l, declare):
+    """`l` with the prototypes of `declare` set on it: the first call per library applies them, later ones are a set lookup"""
+    if declare not in l._declares:
+        declare(l)
+        l._declares.add(declare)
+    return l
+
+
 def lib():
     """Load (once) and return the C-ABI library; fail loudly if it has not been built."""
     global _lib
@@ -119,9 +128,7 @@ def lib():
                         f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(or `make -C deepinv_amd/csrc`). deepinv_amd has no CPU fallback."
                     )
-                l = _DeviceGuardedLib(ctypes.CDLL(LIB_PATH))
-                _declare(l)
-                _lib = l
+                _lib = declare_once(_DeviceGuardedLib(ctypes.CDLL(LIB_PATH)), _declare)
     return _lib
 
 

@@ -13,23 +13,20 @@ import ctypes
 
 import torch
 
-from . import check, lib, ptr, require_hip, stream_ptr
+from . import check, declare_once, lib, ptr, require_hip, stream_ptr
 
 NONE, ABS2, WEIGHT, AMPLITUDE = 0, 1, 2, 3      # DINV_CDENSE_*
 
-_declared = False
+
+def _declare(l):
+    vp, i32, i64, sz, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
+    l.dinv_cdense_workspace_bytes.restype = sz
+    l.dinv_cdense_workspace_bytes.argtypes = [i64, i64, i64]
+    l.dinv_cdense_apply.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, f32, vp, sz, vp]
 
 
 def _l():
-    global _declared
-    l = lib()
-    if not _declared:
-        vp, i32, i64, sz, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
-        l.dinv_cdense_workspace_bytes.restype = sz
-        l.dinv_cdense_workspace_bytes.argtypes = [i64, i64, i64]
-        l.dinv_cdense_apply.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, f32, vp, sz, vp]
-        _declared = True
-    return l
+    return declare_once(lib(), _declare)
 
 
 def _matrix(M: torch.Tensor):

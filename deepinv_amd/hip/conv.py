@@ -6,7 +6,7 @@ import math
 
 import torch
 
-from . import FftPlan, check, f32c, fft_plan, lib, ptr, require_hip, stream_ptr
+from . import FftPlan, check, declare_once, f32c, fft_plan, lib, ptr, require_hip, stream_ptr
 
 _MODES = {"valid": 0, "circular": 1, "reflect": 2, "replicate": 3, "constant": 4, "zeros": 4}
 
@@ -21,31 +21,27 @@ class Conv3dDesc(ctypes.Structure):
                                               "fw", "mode", "reserved")]
 
 
-_declared = False
+def _declare(l):
+    vp, i32, i64, f32, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
+    D, P = ctypes.POINTER(ConvDesc), ctypes.POINTER(FftPlan)
+    l.dinv_conv2d_out_size.argtypes = [D, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    l.dinv_conv2d.argtypes = [D, vp, vp, vp, vp]
+    l.dinv_conv2d_transpose.argtypes = [D, vp, vp, vp, vp]
+    l.dinv_conv2d_filter_grad.argtypes = [D, vp, vp, vp, vp]
+    D3 = ctypes.POINTER(Conv3dDesc)
+    l.dinv_conv3d_out_size.argtypes = [D3, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    for name in ("dinv_conv3d", "dinv_conv3d_transpose", "dinv_conv3d_filter_grad"):
+        getattr(l, name).argtypes = [D3, vp, vp, vp, vp]
+    l.dinv_rfft2.argtypes = [vp, vp, i64, P, vp, P, vp, f32, vp]
+    l.dinv_irfft2.argtypes = [vp, vp, i64, P, vp, P, vp, f32, vp, sz, vp]
+    l.dinv_blurfft_workspace_bytes.restype = sz
+    l.dinv_blurfft_workspace_bytes.argtypes = [i64, i32, i32]
+    l.dinv_blurfft_apply.argtypes = [vp, vp, i64, P, vp, P, vp, vp, vp, i64, i32, f32, f32, vp, sz, vp]
+    l.dinv_spectrum_symbol.argtypes = [vp, vp, i64, i32, i32, vp, vp, i64, i32, f32, vp]
 
 
 def _l():
-    global _declared
-    l = lib()
-    if not _declared:
-        vp, i32, i64, f32, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
-        D, P = ctypes.POINTER(ConvDesc), ctypes.POINTER(FftPlan)
-        l.dinv_conv2d_out_size.argtypes = [D, ctypes.POINTER(i32), ctypes.POINTER(i32)]
-        l.dinv_conv2d.argtypes = [D, vp, vp, vp, vp]
-        l.dinv_conv2d_transpose.argtypes = [D, vp, vp, vp, vp]
-        l.dinv_conv2d_filter_grad.argtypes = [D, vp, vp, vp, vp]
-        D3 = ctypes.POINTER(Conv3dDesc)
-        l.dinv_conv3d_out_size.argtypes = [D3, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
-        for name in ("dinv_conv3d", "dinv_conv3d_transpose", "dinv_conv3d_filter_grad"):
-            getattr(l, name).argtypes = [D3, vp, vp, vp, vp]
-        l.dinv_rfft2.argtypes = [vp, vp, i64, P, vp, P, vp, f32, vp]
-        l.dinv_irfft2.argtypes = [vp, vp, i64, P, vp, P, vp, f32, vp, sz, vp]
-        l.dinv_blurfft_workspace_bytes.restype = sz
-        l.dinv_blurfft_workspace_bytes.argtypes = [i64, i32, i32]
-        l.dinv_blurfft_apply.argtypes = [vp, vp, i64, P, vp, P, vp, vp, vp, i64, i32, f32, f32, vp, sz, vp]
-        l.dinv_spectrum_symbol.argtypes = [vp, vp, i64, i32, i32, vp, vp, i64, i32, f32, vp]
-        _declared = True
-    return l
+    return declare_once(lib(), _declare)
 
 
 def pad_mode(padding: str) -> int:

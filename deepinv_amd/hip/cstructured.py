@@ -19,25 +19,22 @@ import ctypes
 import torch
 import torch.nn.functional as F
 
-from . import FftPlan, check, fft_plan, lib, ptr, require_hip, stream_ptr
+from . import FftPlan, check, declare_once, fft_plan, lib, ptr, require_hip, stream_ptr
 from . import fft as hfft
 from .cdense import ABS2, AMPLITUDE, NONE, WEIGHT, operand, real_operand
 
-_declared = False
+
+def _declare(l):
+    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+    plan = ctypes.POINTER(FftPlan)
+    l.dinv_cstructured_fits.restype = ctypes.c_int
+    l.dinv_cstructured_fits.argtypes = [i32, i32]
+    l.dinv_cstructured_apply.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i64, i32, i32, i32, i32, f32,
+                                         plan, vp, plan, vp, vp]
 
 
 def _l():
-    global _declared
-    l = lib()
-    if not _declared:
-        vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-        plan = ctypes.POINTER(FftPlan)
-        l.dinv_cstructured_fits.restype = ctypes.c_int
-        l.dinv_cstructured_fits.argtypes = [i32, i32]
-        l.dinv_cstructured_apply.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i64, i32, i32, i32, i32, f32,
-                                             plan, vp, plan, vp, vp]
-        _declared = True
-    return l
+    return declare_once(lib(), _declare)
 
 
 def fits(H: int, W: int) -> bool:

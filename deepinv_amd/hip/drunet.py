@@ -6,7 +6,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import check, lib, ptr, stream_ptr
+from . import check, declare_once, lib, ptr, stream_ptr
 
 
 class ActGeom(ctypes.Structure):
@@ -17,7 +17,6 @@ class ActGeom(ctypes.Structure):
     ]
 
 
-_declared = False
 # tuning constants of the fp32 setting (module attributes, no environment knobs): output tile of the Winograd kernel the
 # ResBlock convolutions take (4: csrc/drunet_wino4.hip, 2: csrc/drunet_wino.hip) and the fewest workgroup tiles (64 couts x
 # 32 tile positions) a launch must have for the F(4x4,3x3) kernel (one persistent workgroup per CU: 256 on MI355X)
@@ -32,49 +31,48 @@ FP32_WINOGRAD4_BF16X3 = False
 WINOGRAD4_TAIL_SPLIT = True
 
 
+def _declare(l):
+    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
+    G = ctypes.POINTER(ActGeom)
+    l.dinv_act_geom_init.argtypes = [i32, i32, i32, G]
+    l.dinv_act_pack.argtypes = [G, vp, i32, vp, i32, f32, vp, vp]
+    l.dinv_act_unpack.argtypes = [G, vp, i32, vp, vp]
+    l.dinv_conv3x3.argtypes = [G, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]
+    l.dinv_conv3x3_tail.argtypes = [G, vp, vp, vp, i32, i32, vp, vp]
+    if hasattr(l, "dinv_conv3x3_winograd"):     # (not part of the host emulation build, tests/emu/Makefile)
+        l.dinv_conv3x3_winograd.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp]
+    l.dinv_conv3x3_winograd4.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp, ctypes.c_size_t, vp]
+    l.dinv_conv3x3_winograd4_bf16x3.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp, ctypes.c_size_t, vp]
+    l.dinv_conv3x3_winograd4_workspace_bytes.restype = ctypes.c_size_t
+    l.dinv_conv3x3_winograd4_workspace_bytes.argtypes = []
+    l.dinv_conv3x3_winograd4_last_split.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    l.dinv_conv3x3_split.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp]
+    l.dinv_conv3x3_wsplit.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp]
+    l.dinv_conv3x3x3_split.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, i32, vp]
+    l.dinv_conv3x3x3.argtypes = [G, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp]
+    l.dinv_conv_down2x2.argtypes = [G, G, vp, vp, i32, i32, vp, vp]
+    l.dinv_conv_down2x2_bf16s.argtypes = [G, G, vp, vp, i32, i32, vp, vp]
+    l.dinv_conv_down2x2_bf16x3.argtypes = [G, G, vp, vp, i32, i32, vp, vp]
+    l.dinv_conv_up2x2_bf16s.argtypes = [G, G, vp, vp, vp, i32, i32, vp, vp]
+    l.dinv_conv_wgrad_workspace_bytes.restype = ctypes.c_size_t
+    l.dinv_conv_wgrad_workspace_bytes.argtypes = [G, i32, i32, i32]
+    l.dinv_conv_wgrad.argtypes = [G, G, vp, i32, vp, i32, i32, vp, i32, vp, ctypes.c_size_t, vp]
+    l.dinv_relu_backward.argtypes = [ctypes.c_int64, vp, vp, vp]
+    l.dinv_conv_down2x2_bf16s_3d.argtypes = [G, G, vp, vp, i32, i32, vp, i32, i32, i32, vp]
+    l.dinv_conv_up2x2_bf16s_3d.argtypes = [G, G, vp, vp, vp, i32, i32, vp, i32, i32, vp]
+    l.dinv_conv_wgrad_3d.argtypes = [G, G, vp, i32, vp, i32, vp, i32, vp, ctypes.c_size_t, i32, i32, vp]
+    l.dinv_conv_wgrad_3x3x3.argtypes = [G, vp, i32, vp, i32, ctypes.c_int64, vp, i32, vp, ctypes.c_size_t, vp]
+    l.dinv_conv_up2x2.argtypes = [G, G, vp, vp, vp, i32, i32, vp, vp]
+    l.dinv_conv3x3_bias.argtypes = [G, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp]
+    l.dinv_conv3x3_winograd4_bias.argtypes = [G, vp, vp, vp, i32, i32, vp, i32, vp, ctypes.c_size_t, vp]
+    l.dinv_conv3x3_tail_bias.argtypes = [G, vp, vp, vp, i32, i32, vp, vp, vp]
+    l.dinv_bias_grad_workspace_bytes.restype = ctypes.c_size_t
+    l.dinv_bias_grad_workspace_bytes.argtypes = [G, i32]
+    l.dinv_bias_grad.argtypes = [G, vp, i32, vp, i32, vp, ctypes.c_size_t, vp]
+
+
 def _l():
-    global _declared
-    l = lib()
-    if not _declared:
-        vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-        G = ctypes.POINTER(ActGeom)
-        l.dinv_act_geom_init.argtypes = [i32, i32, i32, G]
-        l.dinv_act_pack.argtypes = [G, vp, i32, vp, i32, f32, vp, vp]
-        l.dinv_act_unpack.argtypes = [G, vp, i32, vp, vp]
-        l.dinv_conv3x3.argtypes = [G, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]
-        l.dinv_conv3x3_tail.argtypes = [G, vp, vp, vp, i32, i32, vp, vp]
-        if hasattr(l, "dinv_conv3x3_winograd"):     # (not part of the host emulation build, tests/emu/Makefile)
-            l.dinv_conv3x3_winograd.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp]
-        l.dinv_conv3x3_winograd4.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp, ctypes.c_size_t, vp]
-        l.dinv_conv3x3_winograd4_bf16x3.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp, ctypes.c_size_t, vp]
-        l.dinv_conv3x3_winograd4_workspace_bytes.restype = ctypes.c_size_t
-        l.dinv_conv3x3_winograd4_workspace_bytes.argtypes = []
-        l.dinv_conv3x3_winograd4_last_split.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
-        l.dinv_conv3x3_split.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp]
-        l.dinv_conv3x3_wsplit.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, vp]
-        l.dinv_conv3x3x3_split.argtypes = [G, vp, vp, i32, i32, vp, vp, i32, i32, vp]
-        l.dinv_conv3x3x3.argtypes = [G, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp]
-        l.dinv_conv_down2x2.argtypes = [G, G, vp, vp, i32, i32, vp, vp]
-        l.dinv_conv_down2x2_bf16s.argtypes = [G, G, vp, vp, i32, i32, vp, vp]
-        l.dinv_conv_down2x2_bf16x3.argtypes = [G, G, vp, vp, i32, i32, vp, vp]
-        l.dinv_conv_up2x2_bf16s.argtypes = [G, G, vp, vp, vp, i32, i32, vp, vp]
-        l.dinv_conv_wgrad_workspace_bytes.restype = ctypes.c_size_t
-        l.dinv_conv_wgrad_workspace_bytes.argtypes = [G, i32, i32, i32]
-        l.dinv_conv_wgrad.argtypes = [G, G, vp, i32, vp, i32, i32, vp, i32, vp, ctypes.c_size_t, vp]
-        l.dinv_relu_backward.argtypes = [ctypes.c_int64, vp, vp, vp]
-        l.dinv_conv_down2x2_bf16s_3d.argtypes = [G, G, vp, vp, i32, i32, vp, i32, i32, i32, vp]
-        l.dinv_conv_up2x2_bf16s_3d.argtypes = [G, G, vp, vp, vp, i32, i32, vp, i32, i32, vp]
-        l.dinv_conv_wgrad_3d.argtypes = [G, G, vp, i32, vp, i32, vp, i32, vp, ctypes.c_size_t, i32, i32, vp]
-        l.dinv_conv_wgrad_3x3x3.argtypes = [G, vp, i32, vp, i32, ctypes.c_int64, vp, i32, vp, ctypes.c_size_t, vp]
-        l.dinv_conv_up2x2.argtypes = [G, G, vp, vp, vp, i32, i32, vp, vp]
-        l.dinv_conv3x3_bias.argtypes = [G, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp]
-        l.dinv_conv3x3_winograd4_bias.argtypes = [G, vp, vp, vp, i32, i32, vp, i32, vp, ctypes.c_size_t, vp]
-        l.dinv_conv3x3_tail_bias.argtypes = [G, vp, vp, vp, i32, i32, vp, vp, vp]
-        l.dinv_bias_grad_workspace_bytes.restype = ctypes.c_size_t
-        l.dinv_bias_grad_workspace_bytes.argtypes = [G, i32]
-        l.dinv_bias_grad.argtypes = [G, vp, i32, vp, i32, vp, ctypes.c_size_t, vp]
-        _declared = True
-    return l
+    return declare_once(lib(), _declare)
 
 
 def geom(batch: int, h: int, w: int) -> ActGeom:

@@ -9,25 +9,22 @@ import ctypes
 
 import torch
 
-from . import FftPlan, check, fft_plan, lib, ptr, require_hip, stream_ptr
+from . import FftPlan, check, declare_once, fft_plan, lib, ptr, require_hip, stream_ptr
 
 MAX_N = 2924        # DINV_DST_MAX_N: the largest row whose odd extension, tables and two line buffers fit the 160 KB of LDS
 
-_declared = False
+
+def _declare(l):
+    vp, i32, i64, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
+    plan = ctypes.POINTER(FftPlan)
+    l.dinv_dst_workspace_bytes.restype = sz
+    l.dinv_dst_workspace_bytes.argtypes = [i64, i32]
+    l.dinv_dst1.argtypes = [vp, vp, i64, i32, plan, vp, vp]
+    l.dinv_structured_apply.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i64, i32, i32, i32, plan, vp, vp]
 
 
 def _l():
-    global _declared
-    l = lib()
-    if not _declared:
-        vp, i32, i64, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
-        plan = ctypes.POINTER(FftPlan)
-        l.dinv_dst_workspace_bytes.restype = sz
-        l.dinv_dst_workspace_bytes.argtypes = [i64, i32]
-        l.dinv_dst1.argtypes = [vp, vp, i64, i32, plan, vp, vp]
-        l.dinv_structured_apply.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i64, i32, i32, i32, plan, vp, vp]
-        _declared = True
-    return l
+    return declare_once(lib(), _declare)
 
 
 def _operand(t: torch.Tensor, what: str) -> torch.Tensor:

@@ -7,29 +7,26 @@ import ctypes
 
 import torch
 
-from . import check, lib, ptr, stream_ptr
+from . import check, declare_once, lib, ptr, stream_ptr
 
-_declared = False
+
+def _declare(l):
+    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+    l.dinv_lincomb.argtypes = [i64, f32, vp, f32, vp, f32, vp, vp, vp]
+    l.dinv_affine.argtypes = [i64, f32, vp, f32, vp, f32, vp, f32, f32, f32, vp, vp]
+    l.dinv_batched_dot_blocks.restype = i32
+    l.dinv_batched_dot_blocks.argtypes = [i64]
+    l.dinv_batched_dot.argtypes = [i32, i64, vp, vp, vp, vp, vp]
+    l.dinv_cg_update.argtypes = [i32, i32, i64, vp, vp, f32, vp, vp, vp, vp, vp]
+    l.dinv_cg_update_masked.argtypes = [i32, i32, i64, vp, vp, f32, vp, vp, vp, vp, vp, vp]
+    l.dinv_cg_check.argtypes = [i32, vp, vp, vp, vp]
+    l.dinv_cdiv_real.argtypes = [i64, i64, vp, vp, f32, vp, vp]
+    l.dinv_mask_solve.argtypes = [i32, i64, i64, vp, vp, f32, vp, vp]
+    l.dinv_fidelity_pointwise.argtypes = [i32, i64, vp, vp, f32, f32, f32, i32, vp, vp]
 
 
 def _l():
-    global _declared
-    l = lib()
-    if not _declared:
-        vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-        l.dinv_lincomb.argtypes = [i64, f32, vp, f32, vp, f32, vp, vp, vp]
-        l.dinv_affine.argtypes = [i64, f32, vp, f32, vp, f32, vp, f32, f32, f32, vp, vp]
-        l.dinv_batched_dot_blocks.restype = i32
-        l.dinv_batched_dot_blocks.argtypes = [i64]
-        l.dinv_batched_dot.argtypes = [i32, i64, vp, vp, vp, vp, vp]
-        l.dinv_cg_update.argtypes = [i32, i32, i64, vp, vp, f32, vp, vp, vp, vp, vp]
-        l.dinv_cg_update_masked.argtypes = [i32, i32, i64, vp, vp, f32, vp, vp, vp, vp, vp, vp]
-        l.dinv_cg_check.argtypes = [i32, vp, vp, vp, vp]
-        l.dinv_cdiv_real.argtypes = [i64, i64, vp, vp, f32, vp, vp]
-        l.dinv_mask_solve.argtypes = [i32, i64, i64, vp, vp, f32, vp, vp]
-        l.dinv_fidelity_pointwise.argtypes = [i32, i64, vp, vp, f32, f32, f32, i32, vp, vp]
-        _declared = True
-    return l
+    return declare_once(lib(), _declare)
 
 
 def eligible(*tensors) -> bool:

@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from . import check, lib, ptr, require_hip, stream_ptr
+from . import check, declare_once, lib, ptr, require_hip, stream_ptr
 
 PRE_MASK, PRE_DAGGER = 1, 2
 SYM_MASK, SYM_MASK2, SYM_PROX, SYM_PROX_ADJ_Y, SYM_DAGGER = 1 << 4, 2 << 4, 3 << 4, 4 << 4, 5 << 4
@@ -20,20 +20,17 @@ MAX_SIDE = 1024
 _TRANSPOSE = {SYM_MASK: PRE_MASK, PRE_MASK: SYM_MASK, SYM_MASK2 | SECOND: SYM_MASK2 | SECOND,
               SYM_MASK2 | NO_TRANSFORM: SYM_MASK2 | NO_TRANSFORM, PRE_DAGGER: SYM_DAGGER, SYM_DAGGER: PRE_DAGGER}
 
-_declared = False
+
+def _declare(l):
+    vp, i32, i64, f32, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
+    l.dinv_hadamard_workspace_bytes.restype = sz
+    l.dinv_hadamard_workspace_bytes.argtypes = [i64, i32, i32]
+    l.dinv_hadamard.argtypes = [vp, vp, i64, i32, i32, i32, f32, vp, sz, vp]
+    l.dinv_hadamard_apply.argtypes = [vp, vp, vp, vp, i64, i32, i32, i64, i32, f32, f32, vp, sz, vp]
 
 
 def _l():
-    global _declared
-    l = lib()
-    if not _declared:
-        vp, i32, i64, f32, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
-        l.dinv_hadamard_workspace_bytes.restype = sz
-        l.dinv_hadamard_workspace_bytes.argtypes = [i64, i32, i32]
-        l.dinv_hadamard.argtypes = [vp, vp, i64, i32, i32, i32, f32, vp, sz, vp]
-        l.dinv_hadamard_apply.argtypes = [vp, vp, vp, vp, i64, i32, i32, i64, i32, f32, f32, vp, sz, vp]
-        _declared = True
-    return l
+    return declare_once(lib(), _declare)
 
 
 def _operand(t: torch.Tensor, what: str) -> torch.Tensor:

@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from . import FftPlan, check, f32c, fft_plan, fft_plan_host_table, lib, ptr, require_hip, stream_ptr
+from . import FftPlan, check, declare_once, f32c, fft_plan, fft_plan_host_table, lib, ptr, require_hip, stream_ptr
 
 
 class RadonDesc(ctypes.Structure):
@@ -27,38 +27,36 @@ class RadonPlan(ctypes.Structure):
 
 
 TILED_MAX_GRID = 4096   # MAXG in csrc/radon_tiled.hip
-_declared = False
+
+
+def _declare(l):
+    vp, i32, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_size_t
+    D, P, F = ctypes.POINTER(RadonDesc), ctypes.POINTER(RadonPlan), ctypes.POINTER(FftPlan)
+    l.dinv_radon_workspace_bytes.restype = sz
+    l.dinv_radon_workspace_bytes.argtypes = [D, i32]
+    l.dinv_radon_forward.argtypes = [D, vp, vp, vp, vp, vp, sz, vp]
+    l.dinv_radon_adjoint.argtypes = [D, vp, vp, vp, vp, vp, sz, vp]
+    l.dinv_radon_ramp.argtypes = [i32, i32, i32, vp, vp, vp]
+    l.dinv_radon_backproject.argtypes = [D, vp, vp, vp, vp, vp, vp]
+    l.dinv_radon_plan_bytes.restype = sz
+    l.dinv_radon_plan_bytes.argtypes = [D]
+    l.dinv_radon_plan_init.argtypes = [D, vp, P, vp]
+    l.dinv_radon_tiled_workspace_bytes.restype = sz
+    l.dinv_radon_tiled_workspace_bytes.argtypes = [D, i32]
+    l.dinv_radon_forward_tiled.argtypes = [D, P, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    l.dinv_radon_adjoint_tiled.argtypes = [D, vp, vp, vp, vp, vp, vp, sz, vp]
+    l.dinv_radon_ramp_padded_size.restype = i32
+    l.dinv_radon_ramp_padded_size.argtypes = [i32]
+    l.dinv_radon_ramp_filter_init.argtypes = [i32, vp, vp]
+    l.dinv_radon_ramp_fft.argtypes = [i32, i32, i32, i32, F, vp, vp, vp, vp, vp]
+    l.dinv_radon_fan_workspace_bytes.restype = sz
+    l.dinv_radon_fan_workspace_bytes.argtypes = [D, i32, i32]
+    l.dinv_radon_fan_forward.argtypes = [D, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    l.dinv_radon_fan_adjoint.argtypes = [D, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
 
 
 def _l():
-    global _declared
-    l = lib()
-    if not _declared:
-        vp, i32, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_size_t
-        D, P, F = ctypes.POINTER(RadonDesc), ctypes.POINTER(RadonPlan), ctypes.POINTER(FftPlan)
-        l.dinv_radon_workspace_bytes.restype = sz
-        l.dinv_radon_workspace_bytes.argtypes = [D, i32]
-        l.dinv_radon_forward.argtypes = [D, vp, vp, vp, vp, vp, sz, vp]
-        l.dinv_radon_adjoint.argtypes = [D, vp, vp, vp, vp, vp, sz, vp]
-        l.dinv_radon_ramp.argtypes = [i32, i32, i32, vp, vp, vp]
-        l.dinv_radon_backproject.argtypes = [D, vp, vp, vp, vp, vp, vp]
-        l.dinv_radon_plan_bytes.restype = sz
-        l.dinv_radon_plan_bytes.argtypes = [D]
-        l.dinv_radon_plan_init.argtypes = [D, vp, P, vp]
-        l.dinv_radon_tiled_workspace_bytes.restype = sz
-        l.dinv_radon_tiled_workspace_bytes.argtypes = [D, i32]
-        l.dinv_radon_forward_tiled.argtypes = [D, P, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-        l.dinv_radon_adjoint_tiled.argtypes = [D, vp, vp, vp, vp, vp, vp, sz, vp]
-        l.dinv_radon_ramp_padded_size.restype = i32
-        l.dinv_radon_ramp_padded_size.argtypes = [i32]
-        l.dinv_radon_ramp_filter_init.argtypes = [i32, vp, vp]
-        l.dinv_radon_ramp_fft.argtypes = [i32, i32, i32, i32, F, vp, vp, vp, vp, vp]
-        l.dinv_radon_fan_workspace_bytes.restype = sz
-        l.dinv_radon_fan_workspace_bytes.argtypes = [D, i32, i32]
-        l.dinv_radon_fan_forward.argtypes = [D, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-        l.dinv_radon_fan_adjoint.argtypes = [D, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-        _declared = True
-    return l
+    return declare_once(lib(), _declare)
 
 
 # test hooks (module attributes, patched by tests/test_tomography_gpu.py to compare kernel generations; not configuration)

@@ -6,22 +6,19 @@ import ctypes
 
 import torch
 
-from . import check, lib, ptr, require_hip, stream_ptr
+from . import check, declare_once, lib, ptr, require_hip, stream_ptr
 
-_declared = False
+
+def _declare(l):
+    vp, i32, i64, u64, f32, f64 = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
+                                   ctypes.c_double)
+    l.dinv_gaussian_noise.argtypes = [i64, i64, vp, vp, f32, u64, u64, vp, vp]
+    l.dinv_poisson_noise.argtypes = [i64, i64, vp, vp, f32, vp, f32, i32, i32, f32, u64, u64, vp, vp, vp]
+    l.dinv_mri_mask_lines.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, f64, i32, u64, u64, vp, vp]
 
 
 def _l():
-    global _declared
-    l = lib()
-    if not _declared:
-        vp, i32, i64, u64, f32, f64 = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
-                                       ctypes.c_double)
-        l.dinv_gaussian_noise.argtypes = [i64, i64, vp, vp, f32, u64, u64, vp, vp]
-        l.dinv_poisson_noise.argtypes = [i64, i64, vp, vp, f32, vp, f32, i32, i32, f32, u64, u64, vp, vp, vp]
-        l.dinv_mri_mask_lines.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, f64, i32, u64, u64, vp, vp]
-        _declared = True
-    return l
+    return declare_once(lib(), _declare)
 
 
 def philox_state(gen: torch.Generator | None, device, n_blocks: int):

@@ -7,24 +7,21 @@ import ctypes
 
 import torch
 
-from . import check, lib, ptr, require_hip, stream_ptr
+from . import check, declare_once, lib, ptr, require_hip, stream_ptr
 from .tv import geometry
 
-_declared = False
+
+def _declare(l):
+    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+    l.dinv_tgv_cp_partials.restype = i32
+    l.dinv_tgv_cp_partials.argtypes = [i64]
+    l.dinv_tgv_cp_iter.argtypes = [i32] * 6 + [vp] * 9 + [f32] * 4 + [vp] * 5
+    for name in ("dinv_tgv_epsilon", "dinv_tgv_epsilon_adjoint"):
+        getattr(l, name).argtypes = [i32, i64, i32, i32, i32, vp, vp, vp]
 
 
 def _l():
-    global _declared
-    l = lib()
-    if not _declared:
-        vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-        l.dinv_tgv_cp_partials.restype = i32
-        l.dinv_tgv_cp_partials.argtypes = [i64]
-        l.dinv_tgv_cp_iter.argtypes = [i32] * 6 + [vp] * 9 + [f32] * 4 + [vp] * 5
-        for name in ("dinv_tgv_epsilon", "dinv_tgv_epsilon_adjoint"):
-            getattr(l, name).argtypes = [i32, i64, i32, i32, i32, vp, vp, vp]
-        _declared = True
-    return l
+    return declare_once(lib(), _declare)
 
 
 class CPState:

@@ -7,26 +7,23 @@ import ctypes
 
 import torch
 
-from . import check, lib, ptr, require_hip, stream_ptr
+from . import check, declare_once, lib, ptr, require_hip, stream_ptr
 
-_declared = False
+
+def _declare(l):
+    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+    l.dinv_tv_cp_partials.restype = i32
+    l.dinv_tv_cp_partials.argtypes = [i64]
+    l.dinv_tv_cp_iter.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, vp, vp]
+    for name in ("dinv_tv_nabla", "dinv_tv_nabla_adjoint", "dinv_tv_grad"):
+        getattr(l, name).argtypes = [i32, i64, i32, i32, i32, vp, vp, vp]
+    l.dinv_tv_fn_blocks.restype = i32
+    l.dinv_tv_fn_blocks.argtypes = [i64]
+    l.dinv_tv_fn.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
 
 
 def _l():
-    global _declared
-    l = lib()
-    if not _declared:
-        vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-        l.dinv_tv_cp_partials.restype = i32
-        l.dinv_tv_cp_partials.argtypes = [i64]
-        l.dinv_tv_cp_iter.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, vp, vp]
-        for name in ("dinv_tv_nabla", "dinv_tv_nabla_adjoint", "dinv_tv_grad"):
-            getattr(l, name).argtypes = [i32, i64, i32, i32, i32, vp, vp, vp]
-        l.dinv_tv_fn_blocks.restype = i32
-        l.dinv_tv_fn_blocks.argtypes = [i64]
-        l.dinv_tv_fn.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
-        _declared = True
-    return l
+    return declare_once(lib(), _declare)
 
 
 def geometry(shape) -> tuple[int, int, int, int, int, int]:

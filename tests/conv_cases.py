@@ -16,19 +16,11 @@ import torch
 
 from fft_cases import POISON, Guarded
 
+from deepinv_amd.hip.conv import Conv3dDesc, ConvDesc
+
 MODES = {"valid": 0, "circular": 1, "reflect": 2, "replicate": 3, "constant": 4}
 LDS_MAX = 64 * 1024               # bytes of dynamic LDS a launcher admits
 MAX_PLANES = 65535                # kMaxGridZ: planes per launch
-
-
-class ConvDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("batch", "channels", "height", "width", "fbatch", "fchannels", "fh", "fw", "mode",
-                                              "stride")]
-
-
-class Conv3dDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("batch", "channels", "depth", "height", "width", "fbatch", "fchannels", "fd", "fh",
-                                              "fw", "mode", "reserved")]
 
 
 # ------------------------------------------------------------------ fp64 references (deepinv's conv2d / conv3d)
@@ -93,8 +85,8 @@ class Conv2:
     mode: str
     stride: int = 1
 
-    def desc(self, cls=ConvDesc):
-        return cls(self.B, self.C, self.H, self.W, self.fb, self.fc, self.fh, self.fw, MODES.get(self.mode, self.mode), self.stride)
+    def desc(self):
+        return ConvDesc(self.B, self.C, self.H, self.W, self.fb, self.fc, self.fh, self.fw, MODES.get(self.mode, self.mode), self.stride)
 
 
 @dataclass(frozen=True)
@@ -111,8 +103,8 @@ class Conv3:
     fw: int
     mode: str
 
-    def desc(self, cls=Conv3dDesc):
-        return cls(self.B, self.C, self.D, self.H, self.W, self.fb, self.fc, self.fd, self.fh, self.fw, MODES.get(self.mode, self.mode), 0)
+    def desc(self):
+        return Conv3dDesc(self.B, self.C, self.D, self.H, self.W, self.fb, self.fc, self.fd, self.fh, self.fw, MODES.get(self.mode, self.mode), 0)
 
 
 def out_size(n, f, mode, s=1):
@@ -377,14 +369,12 @@ CASES = build_cases()
 
 # ------------------------------------------------------------------ the runner
 class Runner:
-    """the C entry points over one library: `lib` (ctypes), `device` of its buffers, `stream()` -> the stream argument, the
-    descriptor classes the library's argtypes name, and - on the emulation - `launches()`, the kernels launched since
-    `reset()`"""
+    """the C entry points over one library: `lib` (ctypes, with the prototypes of deepinv_amd.hip.conv), `device` of its
+    buffers, `stream()` -> the stream argument, and - on the emulation - `launches()`, the kernels launched since `reset()`"""
 
-    def __init__(self, lib, device, stream, desc2=ConvDesc, desc3=Conv3dDesc, reset=None, launches=None):
+    def __init__(self, lib, device, stream, reset=None, launches=None):
         self.lib, self.device, self._stream = lib, torch.device(device), stream
-        self.desc2, self.desc3, self.reset, self.launches = desc2, desc3, reset, launches
-        lib.dinv_last_error.restype = ctypes.c_char_p
+        self.reset, self.launches = reset, launches
 
     def dev(self, t):
         return t.contiguous().to(self.device)
@@ -395,7 +385,7 @@ class Runner:
 
     def call(self, name, d, a, b, out, expect=None):
         """one entry point; out is a tensor or a raw address; asserts the launch log against `expect` where there is one"""
-        desc = d.desc(self.desc3 if isinstance(d, Conv3) else self.desc2)
+        desc = d.desc()
         if self.reset:
             self.reset()
         optr = out if isinstance(out, int) else out.data_ptr()

@@ -10,7 +10,6 @@ hook exists so that the GPU-less build container can drive the real deepinv opti
 (tests/test_dropin_reference.py).  Small problems only: a kernel launch costs seconds."""
 import contextlib
 import ctypes
-import importlib
 
 import torch
 
@@ -20,11 +19,9 @@ import emu_lib
 @contextlib.contextmanager
 def emu_backend():
     import deepinv_amd.hip as H
+    import deepinv_amd.hip.elementwise as EW
 
-    mods = [H] + [importlib.import_module("deepinv_amd.hip." + m) for m in ("mri", "fft", "radon", "conv", "elementwise", "drunet", "random")]
-    emu_lib.lib()                                    # builds the emulation library if needed
-    emu = H._DeviceGuardedLib(ctypes.CDLL(emu_lib.LIB))
-    H._declare(emu)
+    emu = emu_lib.guarded_lib()                      # builds the emulation library if needed
 
     def require(*tensors):
         dev = None
@@ -37,17 +34,6 @@ def emu_backend():
                 raise H.HipExtensionError(f"operands on different devices: {dev} vs {t.device}")
         return dev
 
-    patches = {"lib": lambda: emu, "require_hip": require, "stream_ptr": lambda device: ctypes.c_void_p(0)}
-    saved = []
-    for m in mods:
-        for name, fn in patches.items():
-            if hasattr(m, name):
-                saved.append((m, name, getattr(m, name)))
-                setattr(m, name, fn)
-    saved.append((H, "_lib", H._lib))
-    H._lib = emu
-    EW = importlib.import_module("deepinv_amd.hip.elementwise")
-
     def eligible_on_host(*tensors):   # the fast-path predicate of the loop algebra with "on the HIP device" read as "on the host"
         for t in tensors:
             if t is None:
@@ -58,24 +44,20 @@ def emu_backend():
                 return False
         return True
 
-    saved.append((EW, "eligible", EW.eligible))
-    EW.eligible = eligible_on_host
-    declared = [(m, getattr(m, "_declared")) for m in mods if hasattr(m, "_declared")]
-    for m, _ in declared:
-        m._declared = False                          # optional symbol groups are declared per library
+    # every module of the package took `from . import require_hip, stream_ptr` by name; lib() everywhere returns hip._lib
+    patches = {"require_hip": require, "stream_ptr": lambda device: ctypes.c_void_p(0)}
+    swaps = [(m, name, fn) for m in emu_lib.hip_modules() for name, fn in patches.items() if hasattr(m, name)]
+    swaps += [(H, "_lib", emu), (EW, "eligible", eligible_on_host), (torch.cuda, "current_device", lambda: 0)]
+    saved = [(m, name, getattr(m, name)) for m, name, _ in swaps]
     plan_cache, plan_host = dict(H._plan_cache), dict(H._plan_host)
+    for m, name, fn in swaps:
+        setattr(m, name, fn)
     H._plan_cache.clear()
-    cur = torch.cuda.current_device
-    torch.cuda.current_device = lambda: 0
     try:
         yield emu
     finally:
-        torch.cuda.current_device = cur
         for m, name, fn in saved:
             setattr(m, name, fn)
-        for m, v in declared:
-            m._declared = False
-        H._plan_cache.clear()
-        H._plan_cache.update(plan_cache)
-        H._plan_host.clear()
-        H._plan_host.update(plan_host)
+        for cache, was in ((H._plan_cache, plan_cache), (H._plan_host, plan_host)):
+            cache.clear()
+            cache.update(was)

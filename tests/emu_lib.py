@@ -3,43 +3,58 @@
 (tests/emu/include/hip/hip_runtime.h).  It lets the GPU-less CPU suite execute the real kernel code on small problems
 and compare it with the oracle.  The product never loads this library."""
 import ctypes
+import importlib
 import os
+import pkgutil
 import subprocess
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMU_DIR = os.path.join(HERE, "emu")
-LIB = os.path.join(EMU_DIR, "libdeepinv_amd_emu.so")
+import deepinv_amd.hip as H
+from deepinv_amd.hip import FftPlan  # noqa: F401  (the structures of include/deepinv_amd.h are the product's classes)
+from radon_cases import RadonGeom as _RadonTables
+from radon_cases import FanGeom as _FanTables
 
-MAX_STAGES = 16
-
-
-class FftPlan(ctypes.Structure):
-    _fields_ = [("n", ctypes.c_int32), ("nstages", ctypes.c_int32), ("generic", ctypes.c_int32),
-                ("reserved", ctypes.c_int32), ("radix", ctypes.c_int32 * MAX_STAGES)]
+EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
+_libs = {}
 
 
-from radon_cases import RadonDesc, RadonPlan  # noqa: E402,F401  (the structures of include/deepinv_amd.h)
-from radon_cases import RadonGeom as _RadonTables  # noqa: E402
-from radon_cases import FanGeom as _FanTables  # noqa: E402
+def hip_modules():
+    """every module of deepinv_amd.hip, the package first"""
+    return [H] + [importlib.import_module(m.name) for m in pkgutil.iter_modules(H.__path__, H.__name__ + ".")]
 
-_lib = None
+
+def _load(target):
+    """(the ctypes library, the same behind the product's call wrapper) of one TARGET of tests/emu/Makefile, with every prototype
+    the product declares: each hip module's _declare, so that a direct call here goes through the argtypes the product uses"""
+    if target not in _libs:
+        subprocess.run(["make", "-C", EMU_DIR, "-j8", f"TARGET={target}"], check=True, stdout=subprocess.DEVNULL)
+        cdll = ctypes.CDLL(os.path.join(EMU_DIR, target))
+        guarded = H._DeviceGuardedLib(cdll)
+        for m in hip_modules():
+            if hasattr(m, "_declare"):
+                H.declare_once(guarded, m._declare)
+        cdll.dinv_emu_launch_log_name.restype = cdll.dinv_emu_launch_log_instance.restype = ctypes.c_char_p
+        cdll.dinv_emu_lds_probe.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32]
+        _libs[target] = cdll, guarded
+    return _libs[target]
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        subprocess.run(["make", "-C", EMU_DIR, "-j4"], check=True, stdout=subprocess.DEVNULL)
-        l = ctypes.CDLL(LIB)
-        l.dinv_last_error.restype = ctypes.c_char_p
-        for name in ("dinv_radon_plan_bytes", "dinv_fft_table_bytes"):
-            getattr(l, name).restype = ctypes.c_size_t
-        l.dinv_radon_tiled_workspace_bytes.restype = ctypes.c_size_t
-        l.dinv_radon_workspace_bytes.restype = ctypes.c_size_t
-        _lib = l
-    return _lib
+    """the one emulation library"""
+    return _load("libdeepinv_amd_emu.so")[0]
+
+
+def guarded_lib():
+    """lib() as the product holds a library (hip._DeviceGuardedLib): what tests/emu_backend.py puts in hip._lib"""
+    return _load("libdeepinv_amd_emu.so")[1]
+
+
+def private_copy():
+    """the same objects linked a second time and loaded from a path of their own: a library whose static state (the LDS caps
+    raised so far, the launch log) no other test has touched"""
+    return _load("libdeepinv_amd_emu_private.so")[0]
 
 
 def check(rc):
@@ -130,7 +145,6 @@ class FanGeom(_FanTables):
 
 def radon_fan_forward(x, geo):
     l = lib()
-    l.dinv_radon_fan_workspace_bytes.restype = ctypes.c_size_t
     B, C, W, _ = x.shape
     x = x.contiguous().float()
     d = geo.desc(B * C)
@@ -143,7 +157,6 @@ def radon_fan_forward(x, geo):
 
 def radon_fan_adjoint(y, geo):
     l = lib()
-    l.dinv_radon_fan_workspace_bytes.restype = ctypes.c_size_t
     B, C, N, A = y.shape
     y = y.contiguous().float()
     d = geo.desc(B * C)

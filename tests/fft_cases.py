@@ -267,8 +267,6 @@ class Runner:
 
     def __init__(self, lib, device, plan, stream):
         self.lib, self.device, self._plan, self._stream = lib, torch.device(device), plan, stream
-        lib.dinv_blurfft_workspace_bytes.restype = ctypes.c_size_t
-        lib.dinv_last_error.restype = ctypes.c_char_p
 
     def check(self, rc):
         if rc != 0:

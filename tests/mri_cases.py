@@ -18,18 +18,7 @@ import torch
 import fft_cases as F
 from fft_cases import Guarded       # the guarded buffers of the FFT table
 
-
-class FftPlan(ctypes.Structure):
-    """dinv_fft_plan of include/deepinv_amd.h"""
-    _fields_ = [("n", ctypes.c_int32), ("nstages", ctypes.c_int32), ("generic", ctypes.c_int32), ("reserved", ctypes.c_int32),
-                ("radix", ctypes.c_int32 * 16)]
-
-
-class MriDesc(ctypes.Structure):
-    """dinv_mri_desc of include/deepinv_amd.h (the emulation's twin of deepinv_amd.hip.MriDesc)"""
-    _fields_ = [("batch", ctypes.c_int32), ("coils", ctypes.c_int32), ("ndim", ctypes.c_int32), ("dims", ctypes.c_int32 * 3),
-                ("mask_batch", ctypes.c_int32), ("maps_batch", ctypes.c_int32), ("coil_dim", ctypes.c_int32),
-                ("reserved", ctypes.c_int32), ("plan", FftPlan * 3), ("table", ctypes.c_void_p * 3)]
+from deepinv_amd.hip import MriDesc
 
 
 # ------------------------------------------------------------------ fp64 references (deepinv/physics/mri.py:254-324)
@@ -476,15 +465,13 @@ def err_between(c, a, b, maps, mask, x):
 
 # ------------------------------------------------------------------ the runner
 class Runner:
-    """the C entry points over one library: `lib` (ctypes), `device` of its buffers, `stream()` -> the stream argument,
-    `fft_plan(n)` -> (plan struct, table tensor on the device), the descriptor class the library's argtypes name, and - on
-    the emulation - `reset()` / `launches()`, the instantiations launched since the last reset"""
+    """the C entry points over one library: `lib` (ctypes, with the prototypes of deepinv_amd.hip), `device` of its buffers,
+    `stream()` -> the stream argument, `fft_plan(n)` -> (plan struct, table tensor on the device), and - on the emulation -
+    `reset()` / `launches()`, the instantiations launched since the last reset"""
 
-    def __init__(self, lib, device, stream, fft_plan, desc=MriDesc, reset=None, launches=None):
-        self.lib, self.device, self._stream, self.fft_plan, self.desc_cls = lib, torch.device(device), stream, fft_plan, desc
+    def __init__(self, lib, device, stream, fft_plan, reset=None, launches=None):
+        self.lib, self.device, self._stream, self.fft_plan = lib, torch.device(device), stream, fft_plan
         self.reset, self.launches = reset, launches
-        lib.dinv_last_error.restype = ctypes.c_char_p
-        lib.dinv_mri_workspace_bytes.restype = ctypes.c_size_t
         self.keep = []
 
     def err(self):
@@ -502,12 +489,12 @@ class Runner:
         return d
 
     def desc(self, c):
-        d = self.desc_cls()
+        d = MriDesc()
         d.batch, d.coils, d.ndim = c.B, c.N, len(c.vol)
         for i, n in enumerate(c.vol):
             d.dims[i] = n
             plan, table = self.fft_plan(n)
-            d.plan[i] = type(d.plan[i]).from_buffer_copy(plan)      # (plan classes of the same layout)
+            d.plan[i] = plan
             d.table[i] = table.data_ptr()
             self.keep.append(table)
         d.mask_batch, d.maps_batch, d.coil_dim, d.reserved = c.mask_b, c.maps_b, c.coil_dim, c.hook
@@ -659,7 +646,7 @@ def _rejections(r):
     mk("ndim-4", lambda d: setattr(d, "ndim", 4))
     mk("coils-0", lambda d: setattr(d, "coils", 0))
     mk("coil-dim-0-two-coils", lambda d: setattr(d, "coil_dim", 0))
-    mk("plan-dims-mismatch", lambda d: d.plan.__setitem__(1, type(d.plan[1]).from_buffer_copy(r.fft_plan(128)[0])))
+    mk("plan-dims-mismatch", lambda d: d.plan.__setitem__(1, r.fft_plan(128)[0]))
     mk("null-table", lambda d: d.table.__setitem__(1, None))
     mk("mask-batch-2-of-3", lambda d: setattr(d, "mask_batch", 2))
     mk("maps-batch-without-pointer", maps=False)

@@ -22,25 +22,14 @@ import torch
 
 from fft_cases import POISON, Guarded
 
+from deepinv_amd.hip.radon import RadonDesc, RadonPlan
+
 U = 2.0 ** -24
 TILED_MAX_GRID = 4096             # MAXG of csrc/radon_tiled.hip
 RAMP_FFT_MAX_P = 8192             # deepinv_amd/hip/radon.py
 MAX_LDS = 160 * 1024              # kMaxLdsBytes
 GATHER_LDS = 64 * 1024            # the LDS tables of the first-generation kernels
 MAX_IMAGES = 65535                # images per ramp / back-projection call (grid z)
-
-
-class RadonDesc(ctypes.Structure):
-    _fields_ = [("n_img", ctypes.c_int32), ("width", ctypes.c_int32), ("grid", ctypes.c_int32),
-                ("pad_before", ctypes.c_int32), ("n_angles", ctypes.c_int32), ("circle", ctypes.c_int32),
-                ("scale", ctypes.c_float), ("reserved", ctypes.c_int32)]
-
-
-class RadonPlan(ctypes.Structure):
-    _fields_ = [("grid", ctypes.c_int32), ("n_angles", ctypes.c_int32), ("kw", ctypes.c_int32), ("band_h", ctypes.c_int32),
-                ("win_w", ctypes.c_int32), ("n_jblocks", ctypes.c_int32), ("n_bands", ctypes.c_int32),
-                ("n_chunks_plain", ctypes.c_int32), ("n_chunks_swap", ctypes.c_int32), ("fits", ctypes.c_int32),
-                ("blob_words", ctypes.c_int32), ("widest_window", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)]
 
 
 def ulp(x):
@@ -70,15 +59,14 @@ class RadonGeom:
         X = torch.arange(self.A, dtype=torch.float32) * 2.0 / (self.A - 1) - 1.0 if self.A > 1 else torch.zeros(1)
         self.ixtab = (((X + 1.0) / 2) * (self.A - 1)).contiguous()
 
-    def desc(self, n_img, scale=1.0, cls=RadonDesc):
-        return cls(n_img, self.W, self.G, self.pad, self.A, int(self.circle), float(scale), 0)
+    def desc(self, n_img, scale=1.0):
+        return RadonDesc(n_img, self.W, self.G, self.pad, self.A, int(self.circle), float(scale), 0)
 
-    def plan_host(self, lib, n_img, kw=0, desc_cls=RadonDesc, plan_cls=RadonPlan):
+    def plan_host(self, lib, n_img, kw=0):
         """dinv_radon_plan_init: (plan, int32 blob); kw = 1, 2, 4, 8 forces the angles per workgroup, 0 = automatic"""
-        lib.dinv_radon_plan_bytes.restype = ctypes.c_size_t
-        d = self.desc(n_img, cls=desc_cls)
+        d = self.desc(n_img)
         blob = torch.zeros(lib.dinv_radon_plan_bytes(ctypes.byref(d)) // 4, dtype=torch.int32)
-        pl = plan_cls()
+        pl = RadonPlan()
         pl.kw = kw
         rc = lib.dinv_radon_plan_init(ctypes.byref(d), ctypes.c_void_p(self.cs.data_ptr()), ctypes.byref(pl),
                                       ctypes.c_void_p(blob.data_ptr()))
@@ -606,21 +594,14 @@ CASES = build_cases()
 
 # ------------------------------------------------------------------ the runner
 class Runner:
-    """the C entry points over one library: `lib` (ctypes), `device` of its buffers, `stream()` -> the stream argument, the
-    structure classes the library's argtypes name, and - on the emulation - `launches()`, the instantiations launched since
-    `reset()`"""
+    """the C entry points over one library: `lib` (ctypes, with the prototypes of deepinv_amd.hip.radon), `device` of its
+    buffers, `stream()` -> the stream argument, `fft_plan(n)` -> (plan struct, host table), and - on the emulation -
+    `launches()`, the instantiations launched since `reset()`"""
 
-    def __init__(self, lib, device, stream, desc=RadonDesc, plan=RadonPlan, fftplan=None, fft_plan=None, reset=None,
-                 launches=None):
-        self.lib, self.device, self._stream = lib, torch.device(device), stream
-        self.desc_cls, self.plan_cls, self.fftplan_cls, self.fft_plan = desc, plan, fftplan, fft_plan
+    def __init__(self, lib, device, stream, fft_plan=None, reset=None, launches=None):
+        self.lib, self.device, self._stream, self.fft_plan = lib, torch.device(device), stream, fft_plan
         self.reset, self.launches = reset, launches
         self.keep = []
-        lib.dinv_last_error.restype = ctypes.c_char_p
-        for name in ("dinv_radon_workspace_bytes", "dinv_radon_tiled_workspace_bytes", "dinv_radon_fan_workspace_bytes",
-                     "dinv_radon_plan_bytes"):
-            getattr(lib, name).restype = ctypes.c_size_t
-        lib.dinv_radon_ramp_padded_size.restype = ctypes.c_int32
 
     def dev(self, t):
         """a device copy kept alive until the next case: a pointer handed to the library must outlive the launch"""
@@ -656,7 +637,7 @@ class Runner:
         return torch.zeros(max(int(nbytes), 1), dtype=torch.uint8, device=self.device)
 
     def plan(self, geo, n_img, kw=0):
-        pl, blob = geo.plan_host(self.lib, n_img, kw, self.desc_cls, self.plan_cls)
+        pl, blob = geo.plan_host(self.lib, n_img, kw)
         return pl, self.dev(blob[:pl.blob_words])
 
     def ramp_tables(self, N):
@@ -783,7 +764,7 @@ def _run_par(r, case, gen):
     if tiled_f and not case.subset:
         assert min(plan_slack(geo, pl, blob)) >= 1, "a tap without one column of margin inside its planned window"
     want = expected_launches(case, "fwd", kw)
-    d = geo.desc(n, case.scale, r.desc_cls)
+    d = geo.desc(n, case.scale)
     y = Guarded(n * G * A, r.device)
     if tiled_f:
         ws = r.ws(r.lib.dinv_radon_tiled_workspace_bytes(ctypes.byref(d), 0))
@@ -853,7 +834,7 @@ def _run_bp(r, case, gen):
     n, G, A, W = case.n_img, geo.G, geo.A, geo.W
     v = torch.randn(n, G, A, generator=gen)
     vd = r.dev(v)
-    d = geo.desc(n, case.scale, r.desc_cls)
+    d = geo.desc(n, case.scale)
     out = Guarded(n * W * W, r.device)
     call = lambda: r.run("dinv_radon_backproject", ctypes.byref(d), _p(vd), _p(r.dev(geo.xn)), _p(r.dev(geo.cs)),
                          _p(r.dev(geo.ixtab)), _p(out.t), r._stream(), expect=expected_launches(case, "bp"))
@@ -871,7 +852,7 @@ def _run_fan(r, case, gen):
     x = torch.randn(n, W, W, generator=gen)
     v = torch.randn(n, D, A, generator=gen)
     xd, vd = r.dev(x), r.dev(v)
-    d = geo.desc(n, 1.0, r.desc_cls)
+    d = geo.desc(n, 1.0)
     tabs = [r.dev(t) for t in (geo.xm, geo.sc, geo.yd, geo.cs)]
     y = Guarded(n * D * A, r.device)
     ws = r.ws(r.lib.dinv_radon_fan_workspace_bytes(ctypes.byref(d), ctypes.c_int32(D), ctypes.c_int32(0)))
@@ -938,11 +919,11 @@ def _run_reject(r, case, gen):
     if what.startswith("tiled-G4097"):
         geo = RadonGeom((0., 30.), 2897, False)
         assert geo.G == 4097
-        d = geo.desc(1, 1.0, r.desc_cls)
+        d = geo.desc(1, 1.0)
         out = Guarded(geo.G * geo.A if what.endswith("fwd") else geo.W * geo.W, r.device)
         src = fdev(geo.W * geo.W if what.endswith("fwd") else geo.G * geo.A)
         ws = r.ws(1 << 20)
-        pl = r.plan_cls()
+        pl = RadonPlan()
         pl.grid, pl.n_angles, pl.kw = geo.G, geo.A, 1
         if what.endswith("fwd"):
             name, args = "dinv_radon_forward_tiled", (ctypes.byref(d), ctypes.byref(pl), _p(ws), _p(src), _p(r.dev(geo.xn)),
@@ -954,7 +935,7 @@ def _run_reject(r, case, gen):
         assert r.lib.dinv_radon_tiled_workspace_bytes(ctypes.byref(d), ctypes.c_int32(0)) == 0
     elif what in ("plan-mismatch", "bad-kw", "ws-small-tiled-fwd"):
         geo = RadonGeom(uniform(12), 20, False)
-        d = geo.desc(2, 1.0, r.desc_cls)
+        d = geo.desc(2, 1.0)
         other = RadonGeom(uniform(13), 20, False)
         pl, blob = r.plan(other if what == "plan-mismatch" else geo, 2)
         need = r.lib.dinv_radon_tiled_workspace_bytes(ctypes.byref(d), 0)
@@ -968,7 +949,7 @@ def _run_reject(r, case, gen):
         msg = {"plan-mismatch": "plan does not match", "bad-kw": "bad plan", "ws-small-tiled-fwd": "workspace too small"}[what]
     elif what in ("ws-small-tiled-adj", "ws-small-gather-fwd", "ws-small-gather-adj"):
         geo = RadonGeom(uniform(12), 20, True)
-        d = geo.desc(3, 1.0, r.desc_cls)
+        d = geo.desc(3, 1.0)
         adj = what.endswith("adj")
         fn = r.lib.dinv_radon_tiled_workspace_bytes if "tiled" in what else r.lib.dinv_radon_workspace_bytes
         ws = r.ws(fn(ctypes.byref(d), ctypes.c_int32(int(adj))) - 1)
@@ -1001,7 +982,7 @@ def _run_reject(r, case, gen):
     elif what == "bp-65536":
         geo = RadonGeom((10.,), 2, False)
         n = 65536
-        d = geo.desc(n, 1.0, r.desc_cls)
+        d = geo.desc(n, 1.0)
         out = Guarded(n * geo.W * geo.W, r.device)
         name, args = "dinv_radon_backproject", (ctypes.byref(d), _p(fdev(n * geo.G * geo.A)), _p(r.dev(geo.xn)),
                                                 _p(r.dev(geo.cs)), _p(r.dev(geo.ixtab)), _p(out.t))
@@ -1009,7 +990,7 @@ def _run_reject(r, case, gen):
     elif what == "gather-adj-lds":
         # (ceil(G / 2) * 2) * 4 + A * 8 > 64 KiB: G = 4097 with 6144 angles (6143 fit)
         geo = RadonGeom(uniform(6144), 4097, True)
-        d = geo.desc(1, 1.0, r.desc_cls)
+        d = geo.desc(1, 1.0)
         assert ((geo.G + 1) // 2 * 2) * 4 + 6143 * 8 <= GATHER_LDS < ((geo.G + 1) // 2 * 2) * 4 + geo.A * 8
         ws = r.ws(r.lib.dinv_radon_workspace_bytes(ctypes.byref(d), ctypes.c_int32(1)))
         out = Guarded(geo.W * geo.W, r.device)
@@ -1025,7 +1006,7 @@ def _run_reject(r, case, gen):
             geo = FanGeom((0., 40.), 3, True, {"n_detector_pixels": 16376})
             D = geo.n_det
             adj = True
-        d = geo.desc(1, 1.0, r.desc_cls)
+        d = geo.desc(1, 1.0)
         ws = r.ws(r.lib.dinv_radon_fan_workspace_bytes(ctypes.byref(d), ctypes.c_int32(D), ctypes.c_int32(int(adj))))
         out = Guarded(geo.W * geo.W if adj else D * geo.A, r.device)
         src = fdev(D * geo.A if adj else geo.W * geo.W)
@@ -1047,7 +1028,7 @@ def _run_reject(r, case, gen):
 def run_empty(r):
     """B * C = 0: every entry point returns 0, launches nothing and writes nothing"""
     geo = RadonGeom(uniform(12), 20, False)
-    d = geo.desc(0, 1.0, r.desc_cls)
+    d = geo.desc(0, 1.0)
     out = Guarded(16, r.device)
     dummy = r.dev(torch.zeros(16))
     pl, blob = r.plan(geo, 1)
@@ -1061,7 +1042,7 @@ def run_empty(r):
              ("dinv_radon_ramp", (ctypes.c_int32(0), ctypes.c_int32(7), ctypes.c_int32(3), _p(dummy), _p(out.t)))]
     fg = FanGeom(uniform(4), 20, False)
     ftabs = [_p(r.dev(t)) for t in (fg.xm, fg.sc, fg.yd, fg.cs)]
-    fd = fg.desc(0, 1.0, r.desc_cls)
+    fd = fg.desc(0, 1.0)
     for name in ("dinv_radon_fan_forward", "dinv_radon_fan_adjoint"):
         calls.append((name, (ctypes.byref(fd), ctypes.c_int32(fg.n_det), _p(dummy), *ftabs, _p(out.t), _p(dummy), _sz(0))))
     P, plan, table, filt = r.ramp_tables(7)

@@ -23,7 +23,7 @@ def runner():
     from deepinv_amd import hip
     from deepinv_amd.hip import conv
 
-    return K.Runner(conv._l(), DEV, lambda: hip.stream_ptr(DEV), desc2=conv.ConvDesc, desc3=conv.Conv3dDesc)
+    return K.Runner(conv._l(), DEV, lambda: hip.stream_ptr(DEV))
 
 
 @pytest.mark.parametrize("case", K.CASES, ids=lambda c: c.id)

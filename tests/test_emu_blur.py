@@ -8,14 +8,8 @@ import pytest
 import torch
 
 import emu_lib as E
-from conv_cases import _ref_conv, _ref_conv3
+from conv_cases import Conv3dDesc, ConvDesc, _ref_conv, _ref_conv3
 from fft_cases import BLURFFT_FLAGS, _symbol_ref
-
-
-class ConvDesc(ctypes.Structure):
-    _fields_ = [("batch", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
-                ("fbatch", ctypes.c_int32), ("fchannels", ctypes.c_int32), ("fh", ctypes.c_int32), ("fw", ctypes.c_int32),
-                ("mode", ctypes.c_int32), ("stride", ctypes.c_int32)]
 
 
 MODES = {"valid": 0, "circular": 1, "reflect": 2, "replicate": 3, "constant": 4}
@@ -79,11 +73,6 @@ def test_rfft2_irfft2_emulated(H, W):
     assert float((back.double() - x.double()).norm() / x.double().norm()) < 2e-6
 
 
-class Conv3dDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("batch", "channels", "depth", "height", "width", "fbatch", "fchannels", "fd", "fh", "fw",
-                                              "mode", "reserved")]
-
-
 @pytest.mark.parametrize("mode", ["valid", "circular", "reflect", "replicate", "constant"])
 @pytest.mark.parametrize("shape", [(2, 2, 6, 9, 11, 1, 1, 3, 3, 3), (1, 3, 7, 8, 10, 1, 3, 2, 4, 3), (2, 1, 5, 12, 9, 2, 1, 3, 5, 2)])
 def test_conv3d_transpose_and_filter_grad_emulated(mode, shape):
@@ -128,7 +117,6 @@ def test_blurfft_apply_emulated(H, W, Ps):
     ph_ = torch.rand(Ps, H, Wh, generator=gen) * 6.28
     a = torch.polar(torch.ones_like(ph_), ph_).contiguous()
     l = E.lib()
-    l.dinv_blurfft_workspace_bytes.restype = ctypes.c_size_t
     ph, th = E.fft_plan(H)
     pw, tw = E.fft_plan(W)
     nb = l.dinv_blurfft_workspace_bytes(ctypes.c_int64(P), ctypes.c_int32(H), ctypes.c_int32(W))

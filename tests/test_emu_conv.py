@@ -15,7 +15,6 @@ import emu_lib as E
 @pytest.fixture(scope="module")
 def runner():
     l = E.lib()
-    l.dinv_emu_launch_log_name.restype = ctypes.c_char_p
 
     def launches():
         return [l.dinv_emu_launch_log_name(i).decode() for i in range(l.dinv_emu_launch_log_count())]

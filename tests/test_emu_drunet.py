@@ -8,11 +8,7 @@ import torch
 
 import emu_lib as E
 
-
-class ActGeom(ctypes.Structure):
-    _fields_ = [("batch", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("hp", ctypes.c_int32),
-                ("wp", ctypes.c_int32), ("plane", ctypes.c_int64), ("np", ctypes.c_int64), ("sl", ctypes.c_int64),
-                ("cs", ctypes.c_int64)]
+from deepinv_amd.hip.drunet import ActGeom
 
 
 def geom(B, H, W):
@@ -352,7 +348,6 @@ def test_bf16_split_up2x2_matches_fp64(B, H, W, cin, cout, skip):
 
 def _wgrad(gs, gl, s, m, l, n, taps):
     lib = E.lib()
-    lib.dinv_conv_wgrad_workspace_bytes.restype = ctypes.c_size_t
     k = 3 if taps == 9 else 2
     dw = torch.full((m, n, k, k), float("nan"))
     ws = torch.zeros(lib.dinv_conv_wgrad_workspace_bytes(ctypes.byref(gs), m, n, taps), dtype=torch.uint8)
@@ -472,7 +467,6 @@ def test_wgrad_2x2x2_depth_tap(up):
     gs, gl = geom(B * (D + 2), H, W), geom(B * (2 * D + 2), 2 * H, 2 * W)
     sa, la = vol_to_act(small, gs), vol_to_act(big, gl)
     lib = E.lib()
-    lib.dinv_conv_wgrad_workspace_bytes.restype = ctypes.c_size_t
     for dz in range(2):
         dw = torch.full((cs, cl, 2, 2), float("nan"))
         ws = torch.zeros(lib.dinv_conv_wgrad_workspace_bytes(ctypes.byref(gs), cs, cl, 4), dtype=torch.uint8)
@@ -504,7 +498,6 @@ def test_wgrad_3x3x3_one_call_matches_autograd(B, C, D, H, W, cout):
         return a
 
     lib = E.lib()
-    lib.dinv_conv_wgrad_workspace_bytes.restype = ctypes.c_size_t
     sa, la = to_vol(gy), to_vol(x)
     view = lambda a, dz=0: ctypes.c_void_p(a[:, guard + dz * g.plane:].data_ptr())
     dw = torch.full((cout, C, 3, 3, 3), float("nan"))
@@ -743,7 +736,6 @@ def test_winograd4_conv_matches_fp64(B, H, W, cin, cout, mode, split, bf3):
     ya[:, g.sl:g.sl + g.np].view(-1, B, g.hp, g.wp, 8)[:, :, 1:H + 1, 1:W + 1] = float("nan")   # only interiors are written
     wp = pack_winograd4_bf16x3_weight(w) if bf3 else pack_winograd4_weight(w)    # (bf3: U split into three bf16 parts on the host)
     l = E.lib()
-    l.dinv_conv3x3_winograd4_workspace_bytes.restype = ctypes.c_size_t
     ws = torch.zeros(l.dinv_conv3x3_winograd4_workspace_bytes(), dtype=torch.uint8) if split else None
     for _ in range(2 if split else 1):      # twice: the second launch finds the ticket words reset by the first
         if split:

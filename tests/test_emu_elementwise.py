@@ -15,7 +15,6 @@ class EmuEw:
 
     def __init__(self):
         self.l = E.lib()
-        self.l.dinv_batched_dot_blocks.restype = ctypes.c_int32
 
     def lincomb(self, a, x, b=0.0, y=None, c=0.0, z=None):
         out = torch.empty_like(x)

@@ -6,46 +6,21 @@ deepinv/physics/forward.py:1080-1117, 1212-1252).
 The bound against fp64 is the worst-case rounding of the arithmetic, not a measured figure: a transform over L index bits is L
 rounded additions per output, each relative 2^-24, and the scale, the symbol's products and its division add at most four
 more, so the relative l2 error of one transform is at most (L + 4) 2^-24 and of an operator with two transforms twice that."""
-import ctypes
-import os
-import subprocess
-
 import pytest
 import torch
 
 import emu_lib as E
+from emu_backend import emu_backend
+from emu_lib import check, lib
 
-EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-TARGET = "libdeepinv_amd_emu_hadamard.so"
-_lib = None
+from deepinv_amd.hip import hadamard as hhad
+
 
 PRE = lambda m: m
 SYM = lambda m: m << 4
 SECOND, NO_TRANSFORM, LAST_AXIS, NO_NORMALIZE = 0x100, 0x200, 0x400, 0x800
 RESIDENT_LOG2 = lambda c: c << 16
 U = 2.0 ** -24
-
-
-def lib():
-    """fft.hip (dinv_last_error) + hadamard.hip built for the host by tests/emu/Makefile, as a library of their own"""
-    global _lib
-    if _lib is None:
-        subprocess.run(["make", "-C", EMU_DIR, "-j4", "SRCS=fft hadamard", f"TARGET={TARGET}"], check=True,
-                       stdout=subprocess.DEVNULL)
-        l = ctypes.CDLL(os.path.join(EMU_DIR, TARGET))
-        l.dinv_last_error.restype = ctypes.c_char_p
-        vp, i32, i64, f32, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
-        l.dinv_hadamard_workspace_bytes.restype = sz
-        l.dinv_hadamard_workspace_bytes.argtypes = [i64, i32, i32]
-        l.dinv_hadamard.argtypes = [vp, vp, i64, i32, i32, i32, f32, vp, sz, vp]
-        l.dinv_hadamard_apply.argtypes = [vp, vp, vp, vp, i64, i32, i32, i64, i32, f32, f32, vp, sz, vp]
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != 0:
-        raise RuntimeError(f"emu lib error {rc}: {lib().dinv_last_error().decode()}")
 
 
 def hadamard(x, flags=0, scale=1.0):
@@ -120,6 +95,9 @@ def test_plain_transform(shape, c):
     L = bits(*shape[2:])
     got = hadamard(x, f)
     assert rel(got, r_h2(x)) <= (L + 4) * U
+    if not c:                                                    # the product's wrapper makes the same call (it forces no kernel form)
+        with emu_backend():
+            assert torch.equal(hhad.fwht(x), got)
     # un-normalised, and the caller's scale
     got = hadamard(x, f | NO_NORMALIZE, 0.5)
     assert rel(got, 0.5 * r_h2(x) * (shape[2] * shape[3]) ** 0.5) <= (L + 4) * U

@@ -4,14 +4,12 @@ hipFuncSetAttribute recorded a cap for the kernel (tests/emu/include/hip/hip_run
 
 Each family runs the smallest shape whose request crosses the limit, twice: the first call makes exactly one attribute call (one
 kernel instantiation is reached), the second none, both give the same bits, and the result is within the bound the family's own
-emulated tests use.  The library is a copy of its own (a TARGET of tests/emu/Makefile no other test loads), so no other test has
-raised a cap before.  The sizes are those of the launchers, restated: fft_lds_bytes of fft_cases.py, 28 P bytes a line for the
-DST, the tables of both axes and two planes for the structured operator, a 2^14-float tile for Hadamard, (P + 8 (P + 1)) complex
-values for the ramp filter."""
+emulated tests use.  The library is a copy of its own (emu_lib.private_copy: a TARGET of tests/emu/Makefile no other test loads),
+so no other test has raised a cap before.  The sizes are those of the launchers, restated: fft_lds_bytes of fft_cases.py, 28 P
+bytes a line for the DST, the tables of both axes and two planes for the structured operator, a 2^14-float tile for Hadamard,
+(P + 8 (P + 1)) complex values for the ramp filter."""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,33 +19,14 @@ import emu_lib as E
 import fft_cases as F
 import radon_cases as K
 
-EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-TARGET = "libdeepinv_amd_emu_lds_optin.so"
 LIMIT = 48 * 1024                 # kDefaultLdsBytes: the launchers opt in above this
 EMU_LIMIT = 64 * 1024             # what the runtime, and so the emulation, lets through without a cap
 U = 2.0 ** -24
-vp, i32, i64, f32, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
 
 @pytest.fixture(scope="module")
 def lib():
-    subprocess.run(["make", "-C", EMU_DIR, "-j4", "SRCS=fft dst cstructured hadamard radon radon_tiled lds_probe", f"TARGET={TARGET}"],
-                   check=True, stdout=subprocess.DEVNULL)
-    l = ctypes.CDLL(os.path.join(EMU_DIR, TARGET))
-    l.dinv_last_error.restype = ctypes.c_char_p
-    l.dinv_fft_table_bytes.restype = sz
-    l.dinv_fft_table_bytes.argtypes = [i32]
-    plan = ctypes.POINTER(E.FftPlan)
-    l.dinv_fft_plan_init.argtypes = [i32, plan, vp]
-    l.dinv_fft_c2c_axis.argtypes = [vp, vp, i64, i64, plan, vp, i32, i32, f32, vp]
-    l.dinv_dst1.argtypes = [vp, vp, i64, i32, plan, vp, vp]
-    l.dinv_cstructured_apply.argtypes = [vp, vp, vp, vp, i64] + [i32] * 8 + [i64] + [i32] * 4 + [f32, plan, vp, plan, vp, vp]
-    l.dinv_hadamard.argtypes = [vp, vp, i64, i32, i32, i32, f32, vp, sz, vp]
-    l.dinv_radon_ramp_padded_size.restype = i32
-    l.dinv_radon_ramp_filter_init.argtypes = [i32, vp, vp]
-    l.dinv_radon_ramp_fft.argtypes = [i32, i32, i32, i32, plan, vp, vp, vp, vp, vp]
-    l.dinv_emu_lds_probe.argtypes = [vp, sz, i32]
-    return l
+    return E.private_copy()
 
 
 def fft_plan(lib, n):

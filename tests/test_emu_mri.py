@@ -19,7 +19,7 @@ def _desc(B, N, vol, mask, maps, coil_dim=1):
     for i, n in enumerate(vol):
         d.dims[i] = n
         plan, table = E.fft_plan(n)
-        d.plan[i] = type(d.plan[i]).from_buffer_copy(plan)
+        d.plan[i] = plan
         d.table[i] = table.ctypes.data
         keep.append(table)
     d.mask_batch = 0 if mask is None else mask.shape[0]
@@ -31,7 +31,6 @@ def _desc(B, N, vol, mask, maps, coil_dim=1):
 
 def _run(fn, d, *ptrs):
     l = E.lib()
-    l.dinv_mri_workspace_bytes.restype = ctypes.c_size_t
     ws = np.zeros(l.dinv_mri_workspace_bytes(ctypes.byref(d)), np.uint8)
     E.check(getattr(l, fn)(ctypes.byref(d), *ptrs, E.p(ws), ctypes.c_size_t(ws.size), None))
 

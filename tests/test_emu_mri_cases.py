@@ -14,7 +14,6 @@ import mri_cases as K
 @pytest.fixture(scope="module")
 def runner():
     l = E.lib()
-    l.dinv_emu_launch_log_instance.restype = ctypes.c_char_p
 
     def launches():
         return [l.dinv_emu_launch_log_instance(i).decode() for i in range(l.dinv_emu_launch_log_count())]

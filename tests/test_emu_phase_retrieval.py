@@ -1,67 +1,27 @@
 """Phase retrieval on the host emulation of the kernels: deepinv_amd/csrc/cdense.hip and cstructured.hip (with fft.hip for the
-plans and the composed path) built for the host by tests/emu/Makefile as a library of their own, and the product's Python layer
-pointed at it, so the public classes run on CPU tensors with the real kernel code underneath.  The cases and their bounds are
-those of tests/phase_retrieval_cases.py; the kernel-level cases here go to the C entry points directly."""
-import contextlib
+plans and the composed path) built for the host by tests/emu/Makefile, and the product's Python layer pointed at them
+(tests/emu_backend.py), so the public classes run on CPU tensors with the real kernel code underneath.  The cases and their
+bounds are those of tests/phase_retrieval_cases.py; the kernel-level cases here go to the C entry points directly."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from emu_backend import emu_backend
 import phase_retrieval_cases as PC
 from phase_retrieval_cases import C128, GOLD, U, crel, up
 
 import deepinv_amd as dinv
-import deepinv_amd.hip as H
 from deepinv_amd.hip import cdense as hcd
 from deepinv_amd.hip import cstructured as hcs
-from deepinv_amd.hip import fft as hfft
 
-EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-TARGET = "libdeepinv_amd_emu_phase_retrieval.so"
 DEV = torch.device("cpu")
-
-
-@contextlib.contextmanager
-def emu_phase_retrieval():
-    """hip/cdense.py, hip/cstructured.py and hip/fft.py on the emulated library: TEST INFRASTRUCTURE, as tests/emu_backend.py"""
-    subprocess.run(["make", "-C", EMU_DIR, "-j4", "SRCS=fft cdense cstructured", f"TARGET={TARGET}"], check=True, stdout=subprocess.DEVNULL)
-    emu = H._DeviceGuardedLib(ctypes.CDLL(os.path.join(EMU_DIR, TARGET)))
-    emu.dinv_last_error.restype = ctypes.c_char_p
-    emu.dinv_fft_table_bytes.restype = ctypes.c_size_t
-    emu.dinv_fft_table_bytes.argtypes = [ctypes.c_int32]
-    emu.dinv_fft_plan_init.argtypes = [ctypes.c_int32, ctypes.POINTER(H.FftPlan), ctypes.c_void_p]
-    emu.dinv_fft_c2c_axis.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(H.FftPlan),
-                                      ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p]
-    mods = [H, hcd, hcs, hfft]
-    patches = {"lib": lambda: emu, "require_hip": lambda *t: None, "stream_ptr": lambda device: ctypes.c_void_p(0)}
-    saved = [(m, n, getattr(m, n)) for m in mods for n in patches if hasattr(m, n)]
-    for m, n, _ in saved:
-        setattr(m, n, patches[n])
-    saved.append((H, "_lib", H._lib))
-    H._lib = emu
-    hcd._declared = hcs._declared = False
-    cache = dict(H._plan_cache)
-    H._plan_cache.clear()
-    cur = torch.cuda.current_device
-    torch.cuda.current_device = lambda: 0
-    try:
-        yield emu
-    finally:
-        torch.cuda.current_device = cur
-        for m, n, v in saved:
-            setattr(m, n, v)
-        hcd._declared = hcs._declared = False
-        H._plan_cache.clear()
-        H._plan_cache.update(cache)
 
 
 @pytest.fixture(autouse=True, scope="module")
 def _emu():
-    with emu_phase_retrieval() as emu:
+    with emu_backend() as emu:
         yield emu
 
 

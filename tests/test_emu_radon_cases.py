@@ -16,7 +16,6 @@ import radon_cases as K
 @pytest.fixture(scope="module")
 def runner():
     l = E.lib()
-    l.dinv_emu_launch_log_instance.restype = ctypes.c_char_p
 
     def launches():
         return [l.dinv_emu_launch_log_instance(i).decode() for i in range(l.dinv_emu_launch_log_count())]
@@ -30,7 +29,7 @@ def runner():
         plan, table = E.fft_plan(n)
         return plan, torch.from_numpy(table)
 
-    return K.Runner(l, "cpu", lambda: ctypes.c_void_p(0), fftplan=E.FftPlan, fft_plan=fft_plan, reset=reset, launches=launches)
+    return K.Runner(l, "cpu", lambda: ctypes.c_void_p(0), fft_plan=fft_plan, reset=reset, launches=launches)
 
 
 @pytest.mark.parametrize("case", [c for c in K.CASES if c.emu], ids=lambda c: c.id)

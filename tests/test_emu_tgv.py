@@ -1,40 +1,14 @@
 """Total-generalized-variation kernels (deepinv_amd/csrc/tgv.hip) on the host emulation, on small odd shapes, against a float64
 PyTorch restatement of the reference (deepinv/models/tgv.py:93-310): the Chambolle-Pock iteration with its device stopping
 rule and ping-pong buffers, and the epsilon / epsilon^T pair."""
-import ctypes
-import os
-import subprocess
-
 import pytest
 import torch
 
 import emu_lib as E
+from emu_backend import emu_backend
+from emu_lib import check, lib
 
-EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-TARGET = "libdeepinv_amd_emu_tgv.so"
-_lib = None
-
-
-def lib():
-    """fft.hip (dinv_last_error) + tgv.hip built for the host by tests/emu/Makefile, as a library of their own"""
-    global _lib
-    if _lib is None:
-        subprocess.run(["make", "-C", EMU_DIR, "-j4", "SRCS=fft tgv", f"TARGET={TARGET}"], check=True, stdout=subprocess.DEVNULL)
-        l = ctypes.CDLL(os.path.join(EMU_DIR, TARGET))
-        l.dinv_last_error.restype = ctypes.c_char_p
-        vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-        l.dinv_tgv_cp_partials.restype = i32
-        l.dinv_tgv_cp_partials.argtypes = [i64]
-        l.dinv_tgv_cp_iter.argtypes = [i32] * 6 + [vp] * 9 + [f32] * 4 + [vp] * 5
-        for name in ("dinv_tgv_epsilon", "dinv_tgv_epsilon_adjoint"):
-            getattr(l, name).argtypes = [i32, i64, i32, i32, i32, vp, vp, vp]
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != 0:
-        raise RuntimeError(f"emu lib error {rc}: {lib().dinv_last_error().decode()}")
+from deepinv_amd.hip import tgv as htgv
 
 
 def geo(shape):
@@ -229,6 +203,8 @@ def test_epsilon_and_adjoint(shape):
     assert torch.allclose(au.double(), r_epsilon_adjoint(u.double()), atol=1e-6)
     lhs, rhs = float((ev.double() * u.double()).sum()), float((v.double() * au.double()).sum())
     assert abs(lhs - rhs) <= 1e-6 * ev.double().norm() * u.double().norm()
+    with emu_backend():                                          # the product's wrappers make the same calls
+        assert torch.equal(htgv.epsilon(v), ev) and torch.equal(htgv.epsilon_adjoint(u), au)
 
 
 def test_argument_checks():

@@ -1,43 +1,14 @@
 """Total-variation kernels (deepinv_amd/csrc/tv.hip) on the host emulation, on small odd shapes, against a float64 PyTorch
 restatement of the reference (deepinv/models/tv.py:86-218, deepinv/optim/prior.py:485-612): the Chambolle-Pock iteration
 with its device stopping rule and ping-pong buffers, the finite differences, their adjoint, TVPrior.fn and grad."""
-import ctypes
-import os
-import subprocess
-
 import pytest
 import torch
 
 import emu_lib as E
+from emu_backend import emu_backend
+from emu_lib import check, lib
 
-EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-TARGET = "libdeepinv_amd_emu_tv.so"
-_lib = None
-
-
-def lib():
-    """fft.hip (dinv_last_error) + tv.hip built for the host by tests/emu/Makefile, as a library of their own"""
-    global _lib
-    if _lib is None:
-        subprocess.run(["make", "-C", EMU_DIR, "-j4", "SRCS=fft tv", f"TARGET={TARGET}"], check=True, stdout=subprocess.DEVNULL)
-        l = ctypes.CDLL(os.path.join(EMU_DIR, TARGET))
-        l.dinv_last_error.restype = ctypes.c_char_p
-        vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-        l.dinv_tv_cp_partials.restype = i32
-        l.dinv_tv_cp_partials.argtypes = [i64]
-        l.dinv_tv_cp_iter.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, vp, vp]
-        for name in ("dinv_tv_nabla", "dinv_tv_nabla_adjoint", "dinv_tv_grad"):
-            getattr(l, name).argtypes = [i32, i64, i32, i32, i32, vp, vp, vp]
-        l.dinv_tv_fn_blocks.restype = i32
-        l.dinv_tv_fn_blocks.argtypes = [i64]
-        l.dinv_tv_fn.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != 0:
-        raise RuntimeError(f"emu lib error {rc}: {lib().dinv_last_error().decode()}")
+from deepinv_amd.hip import tv as htv
 
 
 def geo(shape):
@@ -179,12 +150,16 @@ def test_nabla_adjoint_grad_fn(shape):
     n = dx.norm(dim=-1, keepdim=True)
     ref = r_nabla_adjoint(torch.where(n > 0, dx / torch.where(n > 0, n, torch.ones_like(n)), torch.zeros_like(dx)))
     assert torch.allclose(gr.double(), ref, atol=1e-5)
+    with emu_backend():                                          # the product's wrappers make the same calls
+        assert torch.equal(htv.nabla(x), gx) and torch.equal(htv.nabla_adjoint(v), av) and torch.equal(htv.grad(x), gr)
     for mode in (0, 1):
         out = torch.empty(B)
         part = torch.empty(B * l.dinv_tv_fn_blocks(x.numel() // B))
         check(l.dinv_tv_fn(nd, mode, B, C, D, H, W, E.p(x), E.p(out), E.p(part), None))
         r = (dx.abs().sum(-1) if mode else dx.norm(dim=-1)).reshape(B, -1).sum(-1)
         assert torch.allclose(out.double(), r, rtol=1e-5)
+        with emu_backend():
+            assert torch.equal(htv.fn(x, l1=bool(mode)), out)
 
 
 def test_argument_checks():

@@ -246,7 +246,7 @@ def runner(dev):
     import mri_cases as K
     from deepinv_amd import hip
 
-    return K.Runner(hip.lib(), dev, lambda: hip.stream_ptr(dev), lambda n: hip.fft_plan(n, dev), desc=hip.MriDesc)
+    return K.Runner(hip.lib(), dev, lambda: hip.stream_ptr(dev), lambda n: hip.fft_plan(n, dev))
 
 
 def _table():

@@ -20,8 +20,7 @@ def runner():
     from deepinv_amd import hip
     from deepinv_amd.hip import radon as hr
 
-    return K.Runner(hr._l(), DEV, lambda: hip.stream_ptr(DEV), desc=hr.RadonDesc, plan=hr.RadonPlan, fftplan=hip.FftPlan,
-                    fft_plan=lambda n: (hip.fft_plan(n, DEV)[0], hip.fft_plan_host_table(n)))
+    return K.Runner(hr._l(), DEV, lambda: hip.stream_ptr(DEV), fft_plan=lambda n: (hip.fft_plan(n, DEV)[0], hip.fft_plan_host_table(n)))
 
 
 @pytest.mark.parametrize("case", K.CASES, ids=lambda c: c.id)
