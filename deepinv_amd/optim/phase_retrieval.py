@@ -1,6 +1,6 @@
 """Spectral initialisation and helpers for phase retrieval (reference deepinv/optim/phase_retrieval.py).  With a phase-retrieval
 operator of this package one power iteration is two launches: the forward product with the weights ``T(y)`` as its epilogue, and
-the adjoint."""
+the adjoint; with ptychography it is the operator's ``normal_epilogue``, one pass per image."""
 from __future__ import annotations
 
 from typing import Callable
@@ -74,12 +74,15 @@ def spectral_methods(y: torch.Tensor, physics, x: torch.Tensor = None, n_iter: i
     if not fused:
         diag_T = diag_T.to(x)
     for i in range(n_iter):
-        if fused:
-            x_new = B.apply_epilogue(x, hcd.WEIGHT, diag_T)
+        if fused and hasattr(B, "normal_epilogue"):
+            x_new = B.normal_epilogue(x, hcd.WEIGHT, diag_T)
         else:
-            x_new = physics.B(x)
-            x_new = diag_T * x_new
-        x_new = physics.B_adjoint(x_new)
+            if fused:
+                x_new = B.apply_epilogue(x, hcd.WEIGHT, diag_T)
+            else:
+                x_new = physics.B(x)
+                x_new = diag_T * x_new
+            x_new = physics.B_adjoint(x_new)
         x_new = x_new + lamb * x
         x_new = x_new / torch.linalg.norm(x_new)
         if log:

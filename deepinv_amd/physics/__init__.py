@@ -7,7 +7,8 @@ from .blur import Blur, BlurFFT, Downsampling
 from .singlepixel import SinglePixelCamera
 from .compressed_sensing import CompressedSensing
 from .structured_random import StructuredRandom
-from .phase_retrieval import PhaseRetrieval, RandomPhaseRetrieval, StructuredRandomPhaseRetrieval
+from .phase_retrieval import (PhaseRetrieval, Ptychography, PtychographyLinearOperator, RandomPhaseRetrieval,
+                              StructuredRandomPhaseRetrieval)
 from . import functional
 from . import singlepixel
 from . import generator

@@ -1,9 +1,10 @@
-"""Phase retrieval ``y = |Bx|^2`` (reference deepinv/physics/phase_retrieval.py:17-314).  ``B`` is a complex64 linear operator:
-a dense iid Gaussian matrix on csrc/cdense.hip (hip/cdense.py) or a product of 2-D DFTs and unit-modulus diagonals on
-csrc/cstructured.hip (hip/cstructured.py).  With either of them the modulus, the weights of ``A_vjp`` and of the spectral
-initialiser and the residual of the amplitude loss are epilogues of the forward launch, so ``A`` is one launch and ``A_vjp``,
-``AmplitudeLoss.grad`` and one power iteration are two.  With any other ``LinearPhysics`` the methods are the reference's
-expressions.  Ptychography is not part of this module."""
+"""Phase retrieval ``y = |Bx|^2`` (reference deepinv/physics/phase_retrieval.py:17-539).  ``B`` is a complex64 linear operator:
+a dense iid Gaussian matrix on csrc/cdense.hip (hip/cdense.py), a product of 2-D DFTs and unit-modulus diagonals on
+csrc/cstructured.hip (hip/cstructured.py), or the shifted probes and 2-D DFTs of ptychography on the same file's ptychography
+kernels (hip/ptycho.py).  With any of them the modulus, the weights of ``A_vjp`` and of the spectral initialiser and the residual
+of the amplitude loss are epilogues of the forward launch, so ``A`` is one launch and ``A_vjp``, ``AmplitudeLoss.grad`` and one
+power iteration are two; the ptychography operator has ``normal_epilogue``, which runs forward, pointwise stage and adjoint per
+position inside one workgroup.  With any other ``LinearPhysics`` the methods are the reference's expressions."""
 from __future__ import annotations
 
 import math
@@ -14,6 +15,7 @@ from torch import Tensor
 
 from ..hip import cdense as hcd
 from ..hip import cstructured as hcs
+from ..hip import ptycho as hpt
 from .forward import LinearPhysics, Physics
 from .structured_random import _changes, compare
 
@@ -170,10 +172,111 @@ class _StructuredLinear(LinearPhysics):
         return self._run(y.type(torch.cfloat), True)
 
 
+class PtychographyLinearOperator(LinearPhysics):
+    r"""
+    The linear operator of ptychography (phase_retrieval.py:317-430): :math:`B = [B_1; \dots; B_{n_{img}}]`,
+    :math:`B_l = F \text{diag}(p_l)` with :math:`F` the orthonormal 2-D DFT and :math:`p_l` the probe shifted to position
+    :math:`l`, zero where the shift left the plane.  Same signature, buffers (``shifts``, ``init_probe``, ``probe`` of shape
+    ``[1, n_img, H, W]``) and state-dict keys as the reference; the probe stack is built once, on the host, with the reference's
+    own torch expressions, so the buffer is bit-identical to the reference's.  The kernels read ``probe`` where it lies at every
+    call, float32 or complex64: writing to the buffer changes the operator, as in the reference.
+
+    ``A`` fans an image out to its ``n_img`` diffraction planes in one launch; ``A_adjoint`` and :meth:`normal_epilogue` sum over
+    the positions inside the kernel (:mod:`deepinv_amd.hip.ptycho`), while the plane fits the LDS of a workgroup
+    (:func:`deepinv_amd.hip.cstructured.fits`, squares up to 99 x 99); larger planes take the composed device path.
+
+    Deviation from the reference: ``A_adjoint`` multiplies by the **conjugate** of the probe.  The reference multiplies by the probe
+    itself (phase_retrieval.py:395), which is the adjoint for real probes only.  The two coincide for every probe ``build_probe``
+    makes; for a complex probe this class computes the true adjoint, which ``A_vjp``, the amplitude-loss gradient and the spectral
+    method need.
+
+    Like the reference, the operator works for ``img_size[0] == 1`` only (the reference's broadcast of the probe stack against a
+    multi-channel image fails); another channel count raises ``ValueError``.
+
+    :param tuple img_size: shape (1, H, W) of inputs.
+    :param None, torch.Tensor probe: probe of shape ``img_size``, float32 or complex64; ``None`` is the disk of radius 10 of
+        :func:`build_probe`.
+    :param None, torch.Tensor shifts: integer shifts ``[n_img, 2]``; ``None`` is :func:`generate_shifts` with ``n_img = 25``.
+    :param str device: device of the buffers.
+    """
+
+    def __init__(self, img_size, probe=None, shifts=None, device="cpu", **kwargs):
+        super().__init__(**kwargs)
+        if len(img_size) != 3 or int(img_size[0]) != 1:
+            raise ValueError(f"ptychography works for img_size = (1, H, W) only, as the reference's operator does (its probe stack "
+                             f"[1, n_img, H, W] does not broadcast against more channels); got {tuple(img_size)}")
+        self.img_size = img_size
+        if shifts is None:
+            self.n_img = 25
+            shifts = generate_shifts(img_size=img_size, n_img=self.n_img)
+        else:
+            self.n_img = len(shifts)
+        # the stack is built on the host with the reference's expressions and moved once
+        self.register_buffer("shifts", torch.as_tensor(shifts).cpu())
+        if probe is None:
+            probe = build_probe(img_size=img_size, type="disk", probe_radius=10, device="cpu")
+        probe = probe.detach().cpu()
+        if probe.dtype not in (torch.float32, torch.cfloat):
+            raise TypeError(f"the probe must be float32 or complex64, got {probe.dtype}")
+        if tuple(probe.shape) != tuple(int(s) for s in img_size):
+            raise ValueError(f"the probe must have the shape of the image {tuple(img_size)}, got {tuple(probe.shape)}")
+        self.register_buffer("init_probe", probe.clone())
+        probe = probe / self.get_overlap_img(self.shifts).mean().sqrt()
+        probe = torch.cat([self.shift(probe, x_shift, y_shift) for x_shift, y_shift in self.shifts], dim=0).unsqueeze(0)
+        self.register_buffer("probe", probe)
+        self.to(device)
+
+    def measurement_shape(self, x):
+        return (x.shape[0], self.n_img, int(self.img_size[1]), int(self.img_size[2]))
+
+    def _image(self, x):
+        H, W = int(self.img_size[1]), int(self.img_size[2])
+        if x.dim() != 4 or tuple(x.shape[1:]) != (1, H, W):
+            raise ValueError(f"expected an input [batch, 1, {H}, {W}], got shape {tuple(x.shape)}")
+        return x.reshape(-1, H, W)
+
+    def apply_epilogue(self, x: Tensor, epilogue: int, aux=None, eps: float = 1e-12, group: int = 0) -> Tensor:
+        """``B x`` through an epilogue of hip/ptycho.py, in the shape of the measurements"""
+        return hpt.apply(self._image(x), self.probe, hpt.FORWARD, epilogue, aux, eps, group)
+
+    def normal_epilogue(self, x: Tensor, epilogue: int, aux, eps: float = 1e-12, group: int = 0) -> Tensor:
+        """``B^H f(B x, aux)`` with ``f`` the ``WEIGHT`` or ``AMPLITUDE`` epilogue, without the ``n_img``-fold intermediate: what
+        ``A_adjoint(apply_epilogue(x, epilogue, aux, eps))`` computes, position by position inside the workgroup"""
+        return hpt.apply(self._image(x), self.probe, hpt.NORMAL, epilogue, aux, eps, group).unsqueeze(1)
+
+    def A(self, x: Tensor, **kwargs) -> Tensor:
+        return self.apply_epilogue(x, hcd.NONE)
+
+    def A_adjoint(self, y: Tensor, group: int = 0, **kwargs) -> Tensor:
+        return hpt.apply(y.type(torch.cfloat), self.probe, hpt.ADJOINT, hcd.NONE, None, 0.0, group).unsqueeze(1)
+
+    def shift(self, x, x_shift, y_shift, pad_zeros=True):
+        """``x`` rolled by (``x_shift``, ``y_shift``) along the last two axes, with zeros where it wrapped (phase_retrieval.py:397-418)"""
+        x_shift, y_shift = int(x_shift), int(y_shift)
+        x = torch.roll(x, (x_shift, y_shift), dims=(-2, -1))
+        if pad_zeros:
+            if x_shift < 0:
+                x[..., x_shift:, :] = 0
+            elif x_shift > 0:
+                x[..., 0:x_shift, :] = 0
+            if y_shift < 0:
+                x[..., :, y_shift:] = 0
+            elif y_shift > 0:
+                x[..., :, 0:y_shift] = 0
+        return x
+
+    def get_overlap_img(self, shifts):
+        """the summed intensity of the shifted initial probes, whose mean normalises the probe (phase_retrieval.py:420-430)"""
+        overlap_img = torch.zeros_like(self.init_probe, dtype=torch.float32)
+        for x_shift, y_shift in shifts:
+            overlap_img += torch.abs(self.shift(self.init_probe, x_shift, y_shift)) ** 2
+        return overlap_img
+
+
 def fused_operator(physics):
     """the linear operator of a phase-retrieval physics when its epilogues are kernels, else None"""
     B = getattr(physics, "B", None)
-    return B if isinstance(B, (_RandomLinear, _StructuredLinear)) else None
+    return B if isinstance(B, (_RandomLinear, _StructuredLinear, PtychographyLinearOperator)) else None
 
 
 class PhaseRetrieval(Physics):
@@ -217,6 +320,8 @@ class PhaseRetrieval(Physics):
         r""":math:`2 \overline{B}^{\top} \text{diag}(Bx) v`"""
         B = fused_operator(self)
         if B is not None and _real_like(v, B.measurement_shape(x)):
+            if hasattr(B, "normal_epilogue"):
+                return 2 * B.normal_epilogue(x, hcd.WEIGHT, v)
             return 2 * self.B_adjoint(B.apply_epilogue(x, hcd.WEIGHT, v))
         return 2 * self.B_adjoint(self.B(x) * v)
 
@@ -342,3 +447,66 @@ class StructuredRandomPhaseRetrieval(PhaseRetrieval):
     def get_structure(n_layers) -> str:
         """the structure of the operator as a string, e.g. ``"FDFD"``"""
         return "FD" * math.floor(n_layers) + "F" * (n_layers % 1 == 0.5)
+
+
+class Ptychography(PhaseRetrieval):
+    r"""
+    :math:`A(x) = |Bx|^2` with :math:`B` a :class:`PtychographyLinearOperator` (phase_retrieval.py:433-485): the intensities of the
+    diffraction patterns of the image under a probe at ``n_img`` positions.  Same signature and state-dict keys (``B.shifts``,
+    ``B.init_probe``, ``B.probe``) as the reference.  ``B_adjoint`` multiplies by the conjugate of the probe, which differs from
+    the reference for complex probes only (see :class:`PtychographyLinearOperator`).  ``B_dagger`` is not provided.
+
+    :param tuple img_size: shape (1, H, W) of inputs.
+    :param None, torch.Tensor probe: probe of shape ``img_size``; ``None`` is the disk of :func:`build_probe`.
+    :param None, torch.Tensor shifts: shifts ``[n_img, 2]``; ``None`` is :func:`generate_shifts`.
+    :param str device: device of the physics.
+
+    >>> physics = Ptychography(img_size=(1, 64, 64), device="cuda")
+    >>> x = torch.randn((1, 1, 64, 64), dtype=torch.cfloat, device="cuda")
+    >>> physics(x).shape  # 25 probe positions by default
+    torch.Size([1, 25, 64, 64])
+    """
+
+    def __init__(self, img_size=None, probe=None, shifts=None, device="cpu", **kwargs):
+        B = PtychographyLinearOperator(img_size=img_size, probe=probe, shifts=shifts, device=device)
+        self.img_size = img_size
+        super().__init__(B, **kwargs)
+        self.name = "Ptychography_PR"
+        self.to(device)
+
+    @property
+    def probe(self):
+        return self.B.probe
+
+    @property
+    def shifts(self):
+        return self.B.shifts
+
+
+def build_probe(img_size, type="disk", probe_radius=10, device="cpu"):
+    """a probe of shape ``img_size``: for ``"disk"``, one inside the centred disk of ``probe_radius`` and zero outside
+    (phase_retrieval.py:488-511)"""
+    if type == "disk" or type is None:
+        x = torch.arange(img_size[1], dtype=torch.float64)
+        y = torch.arange(img_size[2], dtype=torch.float64)
+        X, Y = torch.meshgrid(x, y, indexing="ij")
+        probe = torch.zeros(tuple(img_size))
+        probe[torch.sqrt((X - img_size[1] // 2) ** 2 + (Y - img_size[2] // 2) ** 2).unsqueeze(0).expand(img_size[0], -1, -1)
+              < probe_radius] = 1
+    else:
+        raise NotImplementedError(f"Probe type {type} not implemented")
+    return probe.to(device)
+
+
+def generate_shifts(img_size, n_img: int = 25, fov: int = None) -> Tensor:
+    """the ``n_img`` probe shifts of a square grid across the field of view, ``[n_img, 2]`` int32 (phase_retrieval.py:514-539)"""
+    if fov is None:
+        fov = img_size[-1]
+    start_shift = -fov // 2
+    end_shift = fov // 2
+    if n_img != int(np.sqrt(n_img)) ** 2:
+        raise ValueError("n_img needs to be a perfect square")
+    side_n_img = int(np.sqrt(n_img))
+    shifts = torch.linspace(start_shift, end_shift, side_n_img).to(torch.int32)
+    y_shifts, x_shifts = torch.meshgrid(shifts, shifts, indexing="ij")
+    return torch.concatenate([x_shifts.reshape(n_img, 1), y_shifts.reshape(n_img, 1)], dim=1)

@@ -35,7 +35,7 @@ typedef void* dinv_stream_t; /* hipStream_t */
 /* library / error                                                            */
 /* ------------------------------------------------------------------------- */
 const char* dinv_last_error(void);
-int dinv_version(void);   /* 16 = this header (adds the complex64 phase-retrieval entry points dinv_cdense_apply and dinv_cstructured_apply); 15: (adds the DST-I / StructuredRandom entry points dinv_dst1, dinv_structured_apply and the dense fp32 product dinv_dense_apply); 14: (adds dinv_poisson_noise and dinv_fidelity_pointwise); 13: (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
+int dinv_version(void);   /* 17 = this header (adds the ptychography entry points dinv_ptycho_apply and dinv_ptycho_workspace_bytes); 16: (adds the complex64 phase-retrieval entry points dinv_cdense_apply and dinv_cstructured_apply); 15: (adds the DST-I / StructuredRandom entry points dinv_dst1, dinv_structured_apply and the dense fp32 product dinv_dense_apply); 14: (adds dinv_poisson_noise and dinv_fidelity_pointwise); 13: (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
 /* number of visible HIP devices (0 when no GPU): used by the host to fail loudly */
 int dinv_device_count(int* count);
 
@@ -800,6 +800,35 @@ int dinv_cstructured_apply(const float* x, float* out, const float* diag, const 
                            int64_t diag_planes, int32_t layers, int32_t half, int32_t adjoint, int32_t epilogue, float eps,
                            const dinv_fft_plan* plan_w, const void* table_w_dev, const dinv_fft_plan* plan_h,
                            const void* table_h_dev, dinv_stream_t stream);
+
+/* dinv_ptycho_apply: the linear operator of ptychography, B = [F diag(p_l)]_{l = 0 .. n_img - 1} with F the orthonormal 2-D DFT of
+ * an H x W plane and p_l the probe at position l (deepinv/physics/phase_retrieval.py:317-395), on the plane-in-LDS scheme of
+ * dinv_cstructured_apply (same fit: dinv_cstructured_fits(H, W), same plans and tables).  `probe` is [n_img, H, W], complex64 when
+ * probe_complex != 0 and fp32 otherwise; it is read where it lies at every call.
+ *     DINV_PTYCHO_FORWARD  x [batch, H, W] -> out [batch, n_img, H, W]:  out[b, l] = epilogue(F (p_l x[b]), aux[b, l]), any of the four
+ *                          epilogues (out is real for DINV_CDENSE_ABS2); one launch, one workgroup per output plane
+ *     DINV_PTYCHO_ADJOINT  x [batch, n_img, H, W] -> out [batch, H, W]:  out[b] = sum_l conj(p_l) F^-1 x[b, l]; epilogue must be
+ *                          DINV_CDENSE_NONE.  conj(p_l) makes this the adjoint for a complex probe too (the reference multiplies by
+ *                          p_l itself, which is the adjoint for real probes only)
+ *     DINV_PTYCHO_NORMAL   x [batch, H, W] -> out [batch, H, W]:  out[b] = sum_l conj(p_l) F^-1 f(F (p_l x[b]), aux[b, l]) with f the
+ *                          DINV_CDENSE_WEIGHT or DINV_CDENSE_AMPLITUDE epilogue, applied in LDS between the two transforms: the
+ *                          [batch, n_img, H, W] intermediate is never stored
+ * aux is real, [batch, n_img, H, W].  The sum over positions of the last two: a workgroup takes image b and `group` consecutive
+ * positions and sums them in registers in position order.  group > 0 forces that many (values above n_img mean n_img); group = 0
+ * picks the largest group that still fills the device, G = ceil(n_img / min(n_img, ceil(S / batch))) with S the compute units times
+ * the workgroups one of them holds at once (2 for planes of at most 4096 elements when two fit its LDS, else 1).  When
+ * one group covers all positions the workgroup stores out itself: one launch.  Otherwise the partial sums [batch, ceil(n_img / G),
+ * H, W] go to `workspace` (dinv_ptycho_workspace_bytes of the same batch, n_img, H, W, op and group; 0 means none is needed and
+ * null is accepted) and a second launch adds them in group order.  No atomics: bit-reproducible for a given group size.  out must
+ * not alias x or aux; the workspace must alias neither x nor out. */
+#define DINV_PTYCHO_FORWARD 0
+#define DINV_PTYCHO_ADJOINT 1
+#define DINV_PTYCHO_NORMAL 2
+size_t dinv_ptycho_workspace_bytes(int64_t batch, int32_t n_img, int32_t H, int32_t W, int32_t op, int32_t group);
+int dinv_ptycho_apply(const float* x, float* out, const void* probe, int32_t probe_complex, const float* aux, int64_t batch,
+                      int32_t n_img, int32_t H, int32_t W, int32_t op, int32_t epilogue, float eps, int32_t group,
+                      const dinv_fft_plan* plan_w, const void* table_w_dev, const dinv_fft_plan* plan_h, const void* table_h_dev,
+                      void* workspace, size_t workspace_bytes, dinv_stream_t stream);
 
 #ifdef __cplusplus
 }
