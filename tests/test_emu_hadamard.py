@@ -1,7 +1,7 @@
 """Walsh-Hadamard kernels (deepinv_amd/csrc/hadamard.hip) on the host emulation: both kernel forms (the resident one and the
-two-pass one, forced on small planes through DINV_HAD_RESIDENT_LOG2) against a float64 restatement written here as dense
-Sylvester matrices, H_H x H_W / sqrt(H W), for every operator of SinglePixelCamera (deepinv/physics/singlepixel.py:408-439 with
-deepinv/physics/forward.py:1080-1117, 1212-1252).
+two-pass one, forced on small planes through DINV_HAD_RESIDENT_LOG2) against the float64 restatement of tests/hadamard_cases.py
+(an fp64 butterfly, H_H x H_W / sqrt(H W)), which also holds the case table, for every operator of SinglePixelCamera
+(deepinv/physics/singlepixel.py:408-439 with deepinv/physics/forward.py:1080-1117, 1212-1252).
 
 The bound against fp64 is the worst-case rounding of the arithmetic, not a measured figure: a transform over L index bits is L
 rounded additions per output, each relative 2^-24, and the scale, the symbol's products and its division add at most four
@@ -12,15 +12,10 @@ import torch
 import emu_lib as E
 from emu_backend import emu_backend
 from emu_lib import check, lib
+from hadamard_cases import (CASES, IDS, LAST_AXIS, NO_NORMALIZE, NO_TRANSFORM, PRE, RESIDENT_LOG2, SECOND, SYM, U, bits, make,
+                            r_h2, r_inv, r_last, rel)
 
 from deepinv_amd.hip import hadamard as hhad
-
-
-PRE = lambda m: m
-SYM = lambda m: m << 4
-SECOND, NO_TRANSFORM, LAST_AXIS, NO_NORMALIZE = 0x100, 0x200, 0x400, 0x800
-RESIDENT_LOG2 = lambda c: c << 16
-U = 2.0 ** -24
 
 
 def hadamard(x, flags=0, scale=1.0):
@@ -36,56 +31,6 @@ def apply(x, mask, flags, y=None, add=0.0, scale=1.0):
     check(lib().dinv_hadamard_apply(E.p(x), E.p(y), E.p(mask), E.p(out), P, H, W, mask.shape[0] * mask.shape[1], flags, add,
                                     scale, None, 0, None))
     return out
-
-
-# ---------------------------------------------------------------- float64 restatement
-def sylvester(n):
-    h = torch.ones(1, 1, dtype=torch.float64)
-    while h.shape[0] < n:
-        h = torch.cat((torch.cat((h, h), 1), torch.cat((h, -h), 1)), 0)
-    return h
-
-
-def r_h2(x):
-    H, W = x.shape[-2:]
-    return sylvester(H) @ x.double() @ sylvester(W) / (H * W) ** 0.5
-
-
-def r_inv(m):
-    return torch.where(m > 1e-5, 1 / m, torch.zeros_like(m))
-
-
-def rel(a, b):
-    return float((a.double() - b).norm() / b.norm().clamp_min(1e-300))
-
-
-def bits(H, W):
-    return (H * W).bit_length() - 1
-
-
-def make(shape, seed, mask_batch=False, binary=True):
-    g = torch.Generator().manual_seed(seed)
-    B, C, H, W = shape
-    x = torch.randn(shape, generator=g)
-    y = torch.randn(shape, generator=g)
-    mshape = (B if mask_batch else 1, C, H, W)
-    if binary:
-        mask = (torch.rand(mshape, generator=g) < 0.4).float()
-    else:
-        mask = torch.rand(mshape, generator=g) * (torch.rand(mshape, generator=g) < 0.7).float()
-    return x, y, mask
-
-
-# (shape [B,C,H,W], resident-limit override or 0).  Resident: the smallest plane, thin planes both ways, groups of 32x32
-# planes with a partial last group (35 planes over groups of 2), groups of 2x2 planes with a partial last group, the largest
-# resident plane.  Two-pass (planes above 2^c floats): the smallest (8 floats over chunks of 4), rectangular both ways, a strip
-# narrower than a chunk (c = 8 with 64 rows: strips of 256 -> 2^14 / 64), P > 1.
-RESIDENT = [((1, 3, 2, 2), 0), ((2, 1, 2, 64), 0), ((2, 1, 64, 2), 0), ((5, 7, 32, 32), 0), ((67, 3, 2, 2), 0),
-            ((1, 1, 128, 128), 0), ((1, 2, 16, 64), 0)]
-TWO_PASS = [((1, 1, 2, 4), 2), ((1, 3, 8, 8), 4), ((2, 1, 4, 32), 3), ((1, 2, 32, 4), 5), ((1, 1, 128, 128), 8),
-            ((2, 1, 64, 64), 11)]
-CASES = RESIDENT + TWO_PASS
-IDS = [f"{'x'.join(map(str, s))}-c{c}" for s, c in CASES]
 
 
 @pytest.mark.parametrize("shape,c", CASES, ids=IDS)
@@ -119,7 +64,7 @@ def test_last_axis(shape, c):
     W = shape[3]
     f = RESIDENT_LOG2(min(c, 14)) if c else 0
     L = W.bit_length() - 1
-    want = x.double() @ sylvester(W)
+    want = r_last(x)
     assert rel(hadamard(x, f | LAST_AXIS), want / W ** 0.5) <= (L + 4) * U
     assert rel(hadamard(x, f | LAST_AXIS | NO_NORMALIZE), want) <= (L + 4) * U
 
