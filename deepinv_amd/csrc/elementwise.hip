@@ -264,6 +264,8 @@ extern "C" int dinv_cg_update(int32_t mode, int32_t batch, int64_t n, const floa
     DINV_REQUIRE(mode == 1 || (v1 && w1), "mode 0 needs r and Ap");
     if (batch == 0 || n == 0) return 0;
     DINV_REQUIRE(batch <= 65535 && n % 4 == 0, "batch too large or n %% 4 != 0");
+    DINV_REQUIRE(((uintptr_t)v0 | (uintptr_t)w0 | (mode == 0 ? (uintptr_t)v1 | (uintptr_t)w1 : (uintptr_t)0)) % 16 == 0,
+                 "cg operands must be 16-byte aligned");
     hipLaunchKernelGGL(cg_update_kernel, dim3(stream_blocks(n), batch), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        mode, n, num, den, eps, v0, v1, w0, w1, (const int32_t*)nullptr);
     DINV_CHECK_LAUNCH();
@@ -277,6 +279,8 @@ extern "C" int dinv_cg_update_masked(int32_t mode, int32_t batch, int64_t n, con
     DINV_REQUIRE(mode == 1 || (v1 && w1), "mode 0 needs r and Ap");
     if (batch == 0 || n == 0) return 0;
     DINV_REQUIRE(batch <= 65535 && n % 4 == 0, "batch too large or n %% 4 != 0");
+    DINV_REQUIRE(((uintptr_t)v0 | (uintptr_t)w0 | (mode == 0 ? (uintptr_t)v1 | (uintptr_t)w1 : (uintptr_t)0)) % 16 == 0,
+                 "cg operands must be 16-byte aligned");
     hipLaunchKernelGGL(cg_update_kernel, dim3(stream_blocks(n), batch), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        mode, n, num, den, eps, v0, v1, w0, w1, done);
     DINV_CHECK_LAUNCH();

@@ -7,82 +7,13 @@ import torch
 import emu_lib as E
 from emu_backend import emu_backend
 from emu_lib import check, lib
+from variational_cases import r_epsilon, r_epsilon_adjoint, r_tgv_prox      # the float64 restatement of the reference
 
 from deepinv_amd.hip import tgv as htgv
 
 
 def geo(shape):
     return (2, shape[0], shape[1], 1, shape[2], shape[3]) if len(shape) == 4 else (3, *shape)
-
-
-# ---------------------------------------------------------------- float64 restatement of the reference
-def r_nabla(x):
-    nd = x.ndim - 2
-    u = torch.zeros((*x.shape, nd), dtype=x.dtype)
-    for i in range(nd):
-        a, b = [slice(None)] * x.ndim, [slice(None)] * x.ndim
-        a[i + 2], b[i + 2] = slice(None, -1), slice(1, None)
-        u[(*a, i)] = x[tuple(b)] - x[tuple(a)]
-    return u
-
-
-def r_nabla_adjoint(v):
-    nd = v.ndim - 3
-    u = torch.zeros(v.shape[:-1], dtype=v.dtype)
-    for i in range(nd):
-        a, b = [slice(None)] * u.ndim, [slice(None)] * u.ndim
-        a[i + 2], b[i + 2] = slice(None, -1), slice(1, None)
-        g = [slice(None)] * v.ndim
-        g[-1], g[i + 2] = i, slice(None, -1)
-        u[tuple(a)] -= v[tuple(g)]
-        u[tuple(b)] += v[tuple(g)]
-    return u
-
-
-def r_epsilon(v):
-    nd = v.ndim - 3
-    out = torch.zeros((*v.shape[:-1], nd * nd), dtype=v.dtype)
-    for i in range(nd):
-        for j in range(nd):
-            a, b = [slice(None)] * (v.ndim - 1), [slice(None)] * (v.ndim - 1)
-            a[j + 2], b[j + 2] = slice(None, -1), slice(1, None)
-            out[(*b, i * nd + j)] = v[(*b, i)] - v[(*a, i)]
-    return out
-
-
-def r_epsilon_adjoint(u):
-    nd = u.ndim - 3
-    out = torch.zeros((*u.shape[:-1], nd), dtype=u.dtype)
-    for i in range(nd):
-        for j in range(nd):
-            a, b = [slice(None)] * (u.ndim - 1), [slice(None)] * (u.ndim - 1)
-            a[j + 2], b[j + 2] = slice(None, -1), slice(1, None)
-            out[(*a, i)] -= u[(*b, i * nd + j)]
-            out[(*b, i)] += u[(*b, i * nd + j)]
-    return out
-
-
-def r_tgv_prox(y, lam, x2, r2, u2, n_it, crit, tau=0.01, rho=1.99):
-    nd = y.ndim - 2
-    sigma = 1 / tau / (72 * (3 if nd == 3 else 1))
-    lam = lam.view(-1, *([1] * (y.ndim - 1)))
-    l1, l2 = 0.1 * lam, 0.15 * lam
-    it_run = 0
-    for it in range(n_it):
-        x_prev = x2
-        t = tau * r_epsilon_adjoint(u2)
-        x = (x2 - r_nabla_adjoint(t) + tau * y) / (1 + tau)
-        s = r2 + t
-        r = s - s / torch.clamp(s.norm(dim=-1) / (tau * l1), min=1.0).unsqueeze(-1)
-        v = u2 + sigma * r_epsilon(r_nabla(2 * x - x2) - (2 * r - r2))
-        u = v / torch.clamp(v.norm(dim=-1) / l2, min=1.0).unsqueeze(-1)
-        x2 = x2 + rho * (x - x2)
-        r2 = r2 + rho * (r - r2)
-        u2 = u2 + rho * (u - u2)
-        it_run = it + 1
-        if it > 1 and float((x_prev - x2).norm() / (x2.norm() + 1e-12)) < crit:
-            break
-    return x2, r2, u2, it_run
 
 
 def run_cp(y, lam, x2, r2, u2, n_launch, crit):

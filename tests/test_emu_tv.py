@@ -7,57 +7,13 @@ import torch
 import emu_lib as E
 from emu_backend import emu_backend
 from emu_lib import check, lib
+from variational_cases import r_nabla, r_nabla_adjoint, r_tv_prox      # the float64 restatement of the reference
 
 from deepinv_amd.hip import tv as htv
 
 
 def geo(shape):
     return (2, shape[0], shape[1], 1, shape[2], shape[3]) if len(shape) == 4 else (3, *shape)
-
-
-# ---------------------------------------------------------------- float64 restatement of the reference
-def r_nabla(x):
-    nd = x.ndim - 2
-    u = torch.zeros((*x.shape, nd), dtype=x.dtype)
-    for i in range(nd):
-        d = i + 2
-        a = [slice(None)] * x.ndim
-        b = [slice(None)] * x.ndim
-        a[d], b[d] = slice(None, -1), slice(1, None)
-        u[(*a, i)] = x[tuple(b)] - x[tuple(a)]
-    return u
-
-
-def r_nabla_adjoint(v):
-    nd = v.ndim - 3
-    u = torch.zeros(v.shape[:-1], dtype=v.dtype)
-    for i in range(nd):
-        d = i + 2
-        a = [slice(None)] * u.ndim
-        b = [slice(None)] * u.ndim
-        a[d], b[d] = slice(None, -1), slice(1, None)
-        g = [slice(None)] * v.ndim
-        g[-1], g[d] = i, slice(None, -1)
-        u[tuple(a)] -= v[tuple(g)]
-        u[tuple(b)] += v[tuple(g)]
-    return u
-
-
-def r_tv_prox(y, lam, x2, u2, n_it, crit, aniso, tau=0.01, rho=1.99):
-    sigma = 1 / tau / 2 ** (y.ndim - 1)
-    lam = lam.view(-1, *([1] * (y.ndim)))
-    it_run = 0
-    for it in range(n_it):
-        x_prev = x2
-        x = (x2 - tau * r_nabla_adjoint(u2) + tau * y) / (1 + tau)
-        u = u2 + sigma * r_nabla(2 * x - x2)
-        u = torch.clamp(u, -lam, lam) if aniso else u / torch.clamp(u.norm(dim=-1, keepdim=True) / lam, min=1.0)
-        x2 = x2 + rho * (x - x2)
-        u2 = u2 + rho * (u - u2)
-        it_run = it + 1
-        if it > 1 and float((x_prev - x2).norm() / (x2 + 1e-12).norm()) < crit:
-            break
-    return x2, u2, it_run
 
 
 def run_cp(y, lam, x2, u2, n_launch, crit, aniso):

@@ -1,13 +1,15 @@
 """Total generalized variation on the MI355X (deepinv_amd/csrc/tgv.hip through deepinv_amd.models.TGVDenoiser) against the
-real reference's outputs (tests/golden/make_golden_tgv.py) and, at full size, against a float64 PyTorch restatement of
-deepinv/models/tgv.py:93-310 written here."""
+real reference's outputs (tests/golden/make_golden_tgv.py) and, at full size, against the float64 PyTorch restatement of
+deepinv/models/tgv.py:93-310 in tests/variational_cases.py."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import variational_cases as VC
 from conftest import rel_err
+from variational_cases import r_epsilon, r_epsilon_adjoint
 
 pytestmark = pytest.mark.gpu
 
@@ -28,72 +30,13 @@ def ths_of(a):
     return float(a) if a.ndim == 0 else a.tolist()
 
 
-# ---------------------------------------------------------------- float64 restatement (tgv.py:93-310)
-def r_nabla(x):
-    nd = x.ndim - 2
-    u = torch.zeros((*x.shape, nd), dtype=x.dtype, device=x.device)
-    for i in range(nd):
-        a, b = [slice(None)] * x.ndim, [slice(None)] * x.ndim
-        a[i + 2], b[i + 2] = slice(None, -1), slice(1, None)
-        u[(*a, i)] = x[tuple(b)] - x[tuple(a)]
-    return u
-
-
-def r_nabla_adjoint(v):
-    nd = v.ndim - 3
-    u = torch.zeros(v.shape[:-1], dtype=v.dtype, device=v.device)
-    for i in range(nd):
-        a, b = [slice(None)] * u.ndim, [slice(None)] * u.ndim
-        a[i + 2], b[i + 2] = slice(None, -1), slice(1, None)
-        gs = [slice(None)] * v.ndim
-        gs[-1], gs[i + 2] = i, slice(None, -1)
-        u[tuple(a)] -= v[tuple(gs)]
-        u[tuple(b)] += v[tuple(gs)]
-    return u
-
-
-def r_epsilon(v):
-    nd = v.ndim - 3
-    out = torch.zeros((*v.shape[:-1], nd * nd), dtype=v.dtype, device=v.device)
-    for i in range(nd):
-        for j in range(nd):
-            a, b = [slice(None)] * (v.ndim - 1), [slice(None)] * (v.ndim - 1)
-            a[j + 2], b[j + 2] = slice(None, -1), slice(1, None)
-            out[(*b, i * nd + j)] = v[(*b, i)] - v[(*a, i)]
-    return out
-
-
-def r_epsilon_adjoint(u):
-    nd = u.ndim - 3
-    out = torch.zeros((*u.shape[:-1], nd), dtype=u.dtype, device=u.device)
-    for i in range(nd):
-        for j in range(nd):
-            a, b = [slice(None)] * (u.ndim - 1), [slice(None)] * (u.ndim - 1)
-            a[j + 2], b[j + 2] = slice(None, -1), slice(1, None)
-            out[(*a, i)] -= u[(*b, i * nd + j)]
-            out[(*b, i)] += u[(*b, i * nd + j)]
-    return out
-
-
-def r_tgv_prox(y, lam, n_it, tau=0.01, rho=1.99):
+# ---------------------------------------------------------------- float64 restatement (tgv.py:93-310): tests/variational_cases.py
+def r_tgv_prox(y, lam, n_it):
+    """n_it iterations from the cold start"""
     nd = y.ndim - 2
-    sigma = 1 / tau / (72 * (3 if nd == 3 else 1))
-    lam = lam.view(-1, *([1] * (y.ndim - 1)))
-    l1, l2 = 0.1 * lam, 0.15 * lam
-    x2 = y.clone()
     r2 = torch.zeros((*y.shape, nd), dtype=y.dtype, device=y.device)
     u2 = torch.zeros((*y.shape, nd * nd), dtype=y.dtype, device=y.device)
-    for _ in range(n_it):
-        t = tau * r_epsilon_adjoint(u2)
-        x = (x2 - r_nabla_adjoint(t) + tau * y) / (1 + tau)
-        s = r2 + t
-        r = s - s / torch.clamp(s.norm(dim=-1) / (tau * l1), min=1.0).unsqueeze(-1)
-        v = u2 + sigma * r_epsilon(r_nabla(2 * x - x2) - (2 * r - r2))
-        u = v / torch.clamp(v.norm(dim=-1) / l2, min=1.0).unsqueeze(-1)
-        x2 = x2 + rho * (x - x2)
-        r2 = r2 + rho * (r - r2)
-        u2 = u2 + rho * (u - u2)
-    return x2, r2, u2
+    return VC.r_tgv_prox(y, lam, y.clone(), r2, u2, n_it, 0.0)[:3]
 
 
 # ---------------------------------------------------------------- parity with the reference

@@ -1,13 +1,15 @@
 """Total variation on the MI355X (deepinv_amd/csrc/tv.hip through deepinv_amd.models.TVDenoiser / TVL1Denoiser and
 deepinv_amd.optim.TVPrior / TVL1Prior) against the real reference's outputs (tests/golden/make_golden_tv.py) and, at the
-project's full sizes, against a float64 PyTorch restatement of deepinv/models/tv.py:86-218 written here."""
+project's full sizes, against the float64 PyTorch restatement of deepinv/models/tv.py:86-218 in tests/variational_cases.py."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import variational_cases as VC
 from conftest import rel_err
+from variational_cases import r_nabla, r_nabla_adjoint
 
 pytestmark = pytest.mark.gpu
 
@@ -24,41 +26,10 @@ def T(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
-# ---------------------------------------------------------------- float64 restatement (tv.py:86-218)
-def r_nabla(x):
-    nd = x.ndim - 2
-    u = torch.zeros((*x.shape, nd), dtype=x.dtype, device=x.device)
-    for i in range(nd):
-        a, b = [slice(None)] * x.ndim, [slice(None)] * x.ndim
-        a[i + 2], b[i + 2] = slice(None, -1), slice(1, None)
-        u[(*a, i)] = x[tuple(b)] - x[tuple(a)]
-    return u
-
-
-def r_nabla_adjoint(v):
-    nd = v.ndim - 3
-    u = torch.zeros(v.shape[:-1], dtype=v.dtype, device=v.device)
-    for i in range(nd):
-        a, b = [slice(None)] * u.ndim, [slice(None)] * u.ndim
-        a[i + 2], b[i + 2] = slice(None, -1), slice(1, None)
-        gs = [slice(None)] * v.ndim
-        gs[-1], gs[i + 2] = i, slice(None, -1)
-        u[tuple(a)] -= v[tuple(gs)]
-        u[tuple(b)] += v[tuple(gs)]
-    return u
-
-
-def r_tv_prox(y, lam, n_it, tau=0.01, rho=1.99):
-    sigma = 1 / tau / 2 ** (y.ndim - 1)
-    lam = lam.view(-1, *([1] * y.ndim))
-    x2, u2 = y.clone(), torch.zeros((*y.shape, y.ndim - 2), dtype=y.dtype, device=y.device)
-    for _ in range(n_it):
-        x = (x2 - tau * r_nabla_adjoint(u2) + tau * y) / (1 + tau)
-        u = u2 + sigma * r_nabla(2 * x - x2)
-        u = u / torch.clamp(u.norm(dim=-1, keepdim=True) / lam, min=1.0)
-        x2 = x2 + rho * (x - x2)
-        u2 = u2 + rho * (u - u2)
-    return x2, u2
+# ---------------------------------------------------------------- float64 restatement (tv.py:86-218): tests/variational_cases.py
+def r_tv_prox(y, lam, n_it):
+    """n_it isotropic iterations from the cold start"""
+    return VC.r_tv_prox(y, lam, y.clone(), torch.zeros((*y.shape, y.ndim - 2), dtype=y.dtype, device=y.device), n_it, 0.0, False)[:2]
 
 
 # ---------------------------------------------------------------- parity with the reference
