@@ -348,6 +348,274 @@ inline int launch_tiled(const ConvGeom& g, bool transpose, const float* in, cons
     return 0;
 }
 
+// ---- Product convolution (SpaceVaryingBlur, deepinv/physics/blur.py:740-868; functional/product_convolution.py:10-68):
+//     A x  = sum_k h_k (*) pad(w_k . x)          A^T y = sum_k w_k . (h_k (*)^T y)          stride 1
+// with multipliers w [mb in {1,B}, mc in {1,C}, K, H, W] and filters h [fb, fc, K, fh, fw].  The reference loops over k in Python
+// and moves about eight image-sized arrays per k (product, convolution, accumulation); here the k loop is INSIDE the kernel and
+// the K-fold intermediate never exists: x (or y), every multiplier once and the result cross memory, (K + 2) H W words.
+struct ProdConv { int32_t K, mb, mc; };
+
+// rows -3 .. h + 2 of one filter as the table tile_chunk walks ([(h + 6)][w4], zero outside the filter), flipped or not
+__device__ __forceinline__ void tile_load_taps(float* __restrict__ kt, const float* __restrict__ kf, int h, int w, int w4, int flip, int tid) {
+    for (int i = tid; i < (h + 6) * w4; i += 256) {
+        const int u = i / w4 - 3, v = i - (u + 3) * w4;
+        float t = 0.f;
+        if (u >= 0 && u < h && v < w) t = flip ? kf[h * w - 1 - (u * w + v)] : kf[u * w + v];
+        kt[i] = t;
+    }
+}
+
+// every chunk of four filter columns of one filter over the thread's 4 x 4 outputs
+__device__ __forceinline__ void tile_filter(f32x2 (&acc)[4][2], const float* __restrict__ pbase, const float* __restrict__ kbase, int pitch,
+                                            int w4, int h, int w) {
+    const int nfull = w >> 2, rem = w & 3;
+    for (int q = 0; q < nfull; ++q) tile_chunk<4>(acc, pbase + 4 * q, kbase + 4 * q, pitch, w4, h);
+    if (rem == 1) tile_chunk<1>(acc, pbase + 4 * nfull, kbase + 4 * nfull, pitch, w4, h);
+    else if (rem == 2) tile_chunk<2>(acc, pbase + 4 * nfull, kbase + 4 * nfull, pitch, w4, h);
+    else if (rem == 3) tile_chunk<3>(acc, pbase + 4 * nfull, kbase + 4 * nfull, pitch, w4, h);
+}
+
+// the thread's 4 x 4 outputs to plane `o`: 16-byte stores where the row allows, scalar ones at a ragged edge
+__device__ __forceinline__ void tile_store(const TileConv& g, const float* out, float* __restrict__ o, int r0, int c0, int tx, int ty,
+                                           const float (&res)[4][4]) {
+    const int oc = c0 + tx * 4;
+    const bool vec = (g.Wo % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0) && (((int64_t)g.Ho * g.Wo) % 4 == 0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int orow = r0 + ty * 4 + i;
+        if (orow >= g.Ho) continue;
+        float* dst = o + (int64_t)orow * g.Wo + oc;
+        if (vec && oc + 3 < g.Wo) {
+            *reinterpret_cast<float4*>(dst) = make_float4(res[i][0], res[i][1], res[i][2], res[i][3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (oc + j < g.Wo) dst[j] = res[i][j];
+        }
+    }
+}
+
+// forward, tiled: per k the staged patch is x[m(p)] w_k[m(p)] (the product BEFORE the padding, m = pad_map) and the filter table is
+// h_k flipped; the 4 x 4 accumulators stay in registers across k, so an output is ONE chain of K h w multiply-adds
+__global__ __launch_bounds__(256) void pconv2d_tiled_kernel(TileConv g, ProdConv p, const float* __restrict__ in,
+                                                            const float* __restrict__ mult, const float* __restrict__ k,
+                                                            float* __restrict__ out) {
+    DINV_DYN_LDS(float, smem);
+    const int w4 = (g.w + 3) & ~3, ph = 64 + g.h - 1;
+    float* kt = smem;                                   // [(h + 6)][w4]
+    float* patch = smem + (g.h + 6) * w4;               // [ph][pitch]
+    const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
+    const int64_t fplane = (int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0);
+    const int64_t mplane = (int64_t)(p.mb > 1 ? b : 0) * p.mc + (p.mc > 1 ? c : 0);
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+    const float* img = in + (int64_t)bc * g.Hi * g.Wi;
+    f32x2 acc[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { acc[i][0] = f32x2{0.f, 0.f}; acc[i][1] = f32x2{0.f, 0.f}; }
+    const float* pbase = patch + (ty * 4) * g.pitch + tx * 4;
+    for (int kk = 0; kk < p.K; ++kk) {
+        const float* wk = mult + (mplane * p.K + kk) * (int64_t)g.Hi * g.Wi;
+        if (kk) __syncthreads();                        // the previous filter's walk has left the table and the patch
+        tile_load_taps(kt, k + (fplane * p.K + kk) * g.h * g.w, g.h, g.w, w4, 1, tid);
+        for (int pr = tid / 64; pr < ph; pr += 4) {
+            const int rr = pad_map(r0 + pr - g.off_r, g.Hi, g.mode);
+            const bool rok = rr >= 0 && rr < g.Hi;
+            for (int pc = tid & 63; pc < g.pw; pc += 64) {
+                const int cc = pad_map(c0 + pc - g.off_c, g.Wi, g.mode);
+                float v = 0.f;
+                if (rok && cc >= 0 && cc < g.Wi) {
+                    const int64_t at = (int64_t)rr * g.Wi + cc;
+                    v = img[at] * wk[at];
+                }
+                patch[pr * g.pitch + pc] = v;
+            }
+        }
+        __syncthreads();
+        tile_filter(acc, pbase, kt + 3 * w4, g.pitch, w4, g.h, g.w);
+    }
+    const float res[4][4] = {{acc[0][0].x, acc[0][0].y, acc[0][1].x, acc[0][1].y}, {acc[1][0].x, acc[1][0].y, acc[1][1].x, acc[1][1].y},
+                             {acc[2][0].x, acc[2][0].y, acc[2][1].x, acc[2][1].y}, {acc[3][0].x, acc[3][0].y, acc[3][1].x, acc[3][1].y}};
+    tile_store(g, out, out + (int64_t)bc * g.Ho * g.Wo, r0, c0, tx, ty, res);
+}
+
+// transposed, tiled (valid / circular / constant: a gather with an index map, see launch_tiled): the y patch does not depend on k and
+// is staged once; every k re-walks it with its own unflipped table into fresh accumulators, and the partial result joins the total
+// with one multiply-add by w_k[r, c]
+__global__ __launch_bounds__(256) void pconv2d_tiled_transpose_kernel(TileConv g, ProdConv p, const float* __restrict__ in,
+                                                                      const float* __restrict__ mult, const float* __restrict__ k,
+                                                                      float* __restrict__ out) {
+    DINV_DYN_LDS(float, smem);
+    const int w4 = (g.w + 3) & ~3, ph = 64 + g.h - 1;
+    float* kt = smem;
+    float* patch = smem + (g.h + 6) * w4;
+    const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
+    const int64_t fplane = (int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0);
+    const int64_t mplane = (int64_t)(p.mb > 1 ? b : 0) * p.mc + (p.mc > 1 ? c : 0);
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+    const float* img = in + (int64_t)bc * g.Hi * g.Wi;
+    for (int pr = tid / 64; pr < ph; pr += 4) {
+        const int rr = pad_map(r0 + pr - g.off_r, g.Hi, g.mode);
+        const bool rok = rr >= 0 && rr < g.Hi;
+        for (int pc = tid & 63; pc < g.pw; pc += 64) {
+            const int cc = pad_map(c0 + pc - g.off_c, g.Wi, g.mode);
+            patch[pr * g.pitch + pc] = (rok && cc >= 0 && cc < g.Wi) ? img[(int64_t)rr * g.Wi + cc] : 0.f;
+        }
+    }
+    float res[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) res[i][j] = 0.f;
+    const float* pbase = patch + (ty * 4) * g.pitch + tx * 4;
+    const int oc = c0 + tx * 4;
+    for (int kk = 0; kk < p.K; ++kk) {
+        if (kk) __syncthreads();                        // the previous filter's walk has left the table
+        tile_load_taps(kt, k + (fplane * p.K + kk) * g.h * g.w, g.h, g.w, w4, 0, tid);
+        __syncthreads();                                // (the first one also publishes the patch)
+        f32x2 acc[4][2];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { acc[i][0] = f32x2{0.f, 0.f}; acc[i][1] = f32x2{0.f, 0.f}; }
+        tile_filter(acc, pbase, kt + 3 * w4, g.pitch, w4, g.h, g.w);
+        const float* wk = mult + (mplane * p.K + kk) * (int64_t)g.Ho * g.Wo;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int orow = r0 + ty * 4 + i;
+            if (orow >= g.Ho) continue;
+            const float* wrow = wk + (int64_t)orow * g.Wo + oc;
+            const float part[4] = {acc[i][0].x, acc[i][0].y, acc[i][1].x, acc[i][1].y};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (oc + j < g.Wo) res[i][j] = fmaf(part[j], wrow[j], res[i][j]);
+        }
+    }
+    tile_store(g, out, out + (int64_t)bc * g.Ho * g.Wo, r0, c0, tx, ty, res);
+}
+
+// forward, general (filters whose tiled form exceeds the LDS budget): conv2d_pad_kernel at stride 1 with the multiplier and the k loop
+__global__ __launch_bounds__(256) void pconv2d_pad_kernel(ConvGeom g, ProdConv p, const float* __restrict__ x, const float* __restrict__ mult,
+                                                          const float* __restrict__ k, float* __restrict__ y) {
+    DINV_DYN_LDS(float, ks);  // flipped filter k of this (b,c)
+    const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
+    const int64_t fplane = (int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0);
+    const int64_t mplane = (int64_t)(p.mb > 1 ? b : 0) * p.mc + (p.mc > 1 ? c : 0);
+    const int jo = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int io = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const bool live = io < g.Ho && jo < g.Wo;
+    const float* img = x + (int64_t)bc * g.H * g.W;
+    float acc = 0.f;
+    for (int kk = 0; kk < p.K; ++kk) {
+        const float* kf = k + (fplane * p.K + kk) * g.h * g.w;
+        const float* wk = mult + (mplane * p.K + kk) * (int64_t)g.H * g.W;
+        if (kk) __syncthreads();
+        for (int i = threadIdx.x; i < g.h * g.w; i += 256) ks[i] = kf[g.h * g.w - 1 - i];
+        __syncthreads();
+        if (!live) continue;
+        for (int u = 0; u < g.h; ++u) {
+            const int r = pad_map(io + u - g.pt, g.H, g.mode);
+            if (r < 0) continue;
+            const float* row = img + (int64_t)r * g.W;
+            const float* wrow = wk + (int64_t)r * g.W;
+            for (int v = 0; v < g.w; ++v) {
+                const int cc = pad_map(jo + v - g.pl, g.W, g.mode);
+                if (cc >= 0) {
+                    const float xw = row[cc] * wrow[cc];
+                    acc = fmaf(ks[u * g.w + v], xw, acc);
+                }
+            }
+        }
+    }
+    if (live) y[((int64_t)bc * g.Ho + io) * g.Wo + jo] = acc;
+}
+
+// transposed, general (reflect / replicate, and filters past the tiled budget): the pre-image gather of conv2d_pad_transpose_kernel at
+// stride 1 per k, the partial result joined to the total with one multiply-add by w_k[r, c]; fixed summation order, no atomics
+__global__ __launch_bounds__(256) void pconv2d_pad_transpose_kernel(ConvGeom g, ProdConv p, const float* __restrict__ y,
+                                                                    const float* __restrict__ mult, const float* __restrict__ k,
+                                                                    float* __restrict__ x) {
+    DINV_DYN_LDS(float, ks);
+    const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
+    const int64_t fplane = (int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0);
+    const int64_t mplane = (int64_t)(p.mb > 1 ? b : 0) * p.mc + (p.mc > 1 ? c : 0);
+    const int cc = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int r = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const bool live = r < g.H && cc < g.W;
+    const float* meas = y + (int64_t)bc * g.Ho * g.Wo;
+    const Pre prow = preimages(r, g.H, g.pt, g.pb, g.mode);
+    const Pre pcol = preimages(cc, g.W, g.pl, g.pr, g.mode);
+    float total = 0.f;
+    for (int kk = 0; kk < p.K; ++kk) {
+        const float* kf = k + (fplane * p.K + kk) * g.h * g.w;
+        if (kk) __syncthreads();
+        for (int i = threadIdx.x; i < g.h * g.w; i += 256) ks[i] = kf[g.h * g.w - 1 - i];
+        __syncthreads();
+        if (!live) continue;
+        float acc = 0.f;
+        // the taps (u, v) that meet a measurement, (pr - u, pc - v) inside y, as ranges worked out before the loops: the inner loop
+        // has no condition, so its loads are independent of the multiply-add chain and can be issued ahead of it
+        for (int ir = 0; ir < prow.n; ++ir)
+            for (int pr = prow.lo[ir]; pr <= prow.hi[ir]; ++pr) {
+                const int u1 = min(g.h - 1, pr);
+                for (int u = max(0, pr - (g.Ho - 1)); u <= u1; ++u) {
+                    const float* mrow = meas + (int64_t)(pr - u) * g.Wo;
+                    const float* krow = ks + u * g.w;
+                    for (int ic = 0; ic < pcol.n; ++ic)
+                        for (int pc = pcol.lo[ic]; pc <= pcol.hi[ic]; ++pc) {
+                            const int v1 = min(g.w - 1, pc);
+#pragma unroll 8
+                            for (int v = max(0, pc - (g.Wo - 1)); v <= v1; ++v) acc = fmaf(krow[v], mrow[pc - v], acc);
+                        }
+                }
+            }
+        total = fmaf(acc, mult[(mplane * p.K + kk) * (int64_t)g.H * g.W + (int64_t)r * g.W + cc], total);
+    }
+    if (live) x[((int64_t)bc * g.H + r) * g.W + cc] = total;
+}
+
+// one launch per call: the tiled kernels wherever launch_tiled takes the plain convolution (the same LDS need), the general ones else
+inline int launch_pconv(const ConvGeom& g, const ProdConv& p, bool transpose, const float* in, const float* mult, const float* k, float* out,
+                        hipStream_t s) {
+    const bool gather = !transpose || g.mode == PAD_VALID || g.mode == PAD_CIRCULAR || g.mode == PAD_CONSTANT;
+    const int w4 = (g.w + 3) & ~3;
+    const size_t lds = ((size_t)(g.h + 6) * w4 + (size_t)(64 + g.h - 1) * (64 + w4)) * sizeof(float);
+    if (gather && lds <= 64 * 1024) {
+        TileConv t;
+        t.C = g.C; t.fb = g.fb; t.fc = g.fc; t.h = g.h; t.w = g.w;
+        t.pw = 64 + w4;
+        t.pitch = t.pw;
+        const dim3 grid(((transpose ? g.W : g.Wo) + 63) / 64, ((transpose ? g.H : g.Ho) + 63) / 64, g.B * g.C);
+        if (!transpose) {
+            t.Hi = g.H; t.Wi = g.W; t.Ho = g.Ho; t.Wo = g.Wo; t.off_r = g.pt; t.off_c = g.pl; t.mode = g.mode; t.flip = 1;
+            if (lds > kDefaultLdsBytes) if (int e = raise_lds_cap<pconv2d_tiled_kernel>(64 * 1024)) return e;
+            hipLaunchKernelGGL(pconv2d_tiled_kernel, grid, dim3(256), lds, s, t, p, in, mult, k, out);
+        } else {        // as launch_tiled: a gather of y with the unflipped filter, zero outside y or periodic
+            t.Hi = g.Ho; t.Wi = g.Wo; t.Ho = g.H; t.Wo = g.W; t.off_r = g.h - 1 - g.pt; t.off_c = g.w - 1 - g.pl;
+            t.mode = g.mode == PAD_CIRCULAR ? PAD_CIRCULAR : PAD_CONSTANT; t.flip = 0;
+            if (lds > kDefaultLdsBytes) if (int e = raise_lds_cap<pconv2d_tiled_transpose_kernel>(64 * 1024)) return e;
+            hipLaunchKernelGGL(pconv2d_tiled_transpose_kernel, grid, dim3(256), lds, s, t, p, in, mult, k, out);
+        }
+    } else if (!transpose) {
+        hipLaunchKernelGGL(pconv2d_pad_kernel, dim3((g.Wo + 63) / 64, (g.Ho + 3) / 4, g.B * g.C), dim3(256), g.h * g.w * sizeof(float), s, g, p,
+                           in, mult, k, out);
+    } else {
+        hipLaunchKernelGGL(pconv2d_pad_transpose_kernel, dim3((g.W + 63) / 64, (g.H + 3) / 4, g.B * g.C), dim3(256),
+                           g.h * g.w * sizeof(float), s, g, p, in, mult, k, out);
+    }
+    DINV_CHECK_LAUNCH();
+    return 0;
+}
+
+int make_pgeom(const dinv_conv_desc* d, int32_t K, int32_t mbatch, int32_t mchannels, ConvGeom* g, ProdConv* p) {
+    DINV_REQUIRE(d != nullptr, "null descriptor");
+    DINV_REQUIRE(d->stride == 1, "product convolution: stride must be 1, got %d", d->stride);
+    DINV_REQUIRE(K >= 1, "product convolution: bad number of filters K = %d", K);
+    if (int e = make_geom(d, g)) return e;
+    DINV_REQUIRE((mbatch == 1 || mbatch == g->B) && (mchannels == 1 || mchannels == g->C), "multiplier shape not broadcastable");
+    p->K = K; p->mb = mbatch; p->mc = mchannels;
+    return 0;
+}
+
 // ---- LDS-tiled forms for stride s >= 2 (Downsampling.A / A_adjoint: bicubic x4 on 256 x 256 is a 16 x 16 filter at stride 4).  The
 // general kernels above read every tap from global memory through pad_map (57 us) or walk pre-image lists with integer divisions and
 // spill (91 us) for 12.6 MB of input: ten times what the bytes cost.  Forward: a workgroup owns 16 x 16 outputs; its
@@ -1021,6 +1289,26 @@ extern "C" int dinv_conv2d_filter_grad(const dinv_conv_desc* d, const float* x, 
                        x, gy, dk_planes);
     DINV_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int dinv_pconv2d(const dinv_conv_desc* d, int32_t K, int32_t mbatch, int32_t mchannels, const float* x, const float* w,
+                            const float* h, float* y, dinv_stream_t stream) {
+    ConvGeom g;
+    ProdConv p;
+    if (int e = make_pgeom(d, K, mbatch, mchannels, &g, &p)) return e;
+    if (g.B == 0) return 0;
+    DINV_REQUIRE(x && w && h && y, "null pointer");
+    return launch_pconv(g, p, false, x, w, h, y, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinv_pconv2d_transpose(const dinv_conv_desc* d, int32_t K, int32_t mbatch, int32_t mchannels, const float* y, const float* w,
+                                      const float* h, float* x, dinv_stream_t stream) {
+    ConvGeom g;
+    ProdConv p;
+    if (int e = make_pgeom(d, K, mbatch, mchannels, &g, &p)) return e;
+    if (g.B == 0) return 0;
+    DINV_REQUIRE(x && w && h && y, "null pointer");
+    return launch_pconv(g, p, true, y, w, h, x, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int dinv_conv3d_out_size(const dinv_conv3d_desc* d, int32_t* dout, int32_t* ho, int32_t* wo) {

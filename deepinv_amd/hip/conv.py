@@ -1,4 +1,5 @@
-"""ctypes + autograd wrappers for csrc/blur.hip (padded convolution, its transpose, rfft2/irfft2)."""
+"""ctypes + autograd wrappers for csrc/blur.hip (padded convolution, its transpose, the product convolution of SpaceVaryingBlur,
+rfft2/irfft2)."""
 from __future__ import annotations
 
 import ctypes
@@ -28,6 +29,8 @@ def _declare(l):
     l.dinv_conv2d.argtypes = [D, vp, vp, vp, vp]
     l.dinv_conv2d_transpose.argtypes = [D, vp, vp, vp, vp]
     l.dinv_conv2d_filter_grad.argtypes = [D, vp, vp, vp, vp]
+    l.dinv_pconv2d.argtypes = [D, i32, i32, i32, vp, vp, vp, vp, vp]
+    l.dinv_pconv2d_transpose.argtypes = [D, i32, i32, i32, vp, vp, vp, vp, vp]
     D3 = ctypes.POINTER(Conv3dDesc)
     l.dinv_conv3d_out_size.argtypes = [D3, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     for name in ("dinv_conv3d", "dinv_conv3d_transpose", "dinv_conv3d_filter_grad"):
@@ -196,6 +199,119 @@ def conv3d(x, filt, padding="valid"):
 
 def conv3d_transpose(y, filt, padding, size):
     return _ConvT.apply(y, filt, padding, 1, tuple(int(v) for v in size))
+
+
+# --------------------------------------------------------------------------- product convolution (SpaceVaryingBlur)
+def _pconv_desc(B, C, size, mult, filt, padding):
+    """descriptor, K and output size of y = sum_k conv(w_k x, h_k) for x [B, C, *size], w [b, c, K, H, W], h [b', c', K, fh, fw]"""
+    if mult.dim() != 5 or filt.dim() != 5:
+        raise ValueError(f"multipliers and filters must be 5D tensors (b, c, K, ., .), got {mult.dim()}D and {filt.dim()}D")
+    if mult.is_complex() or filt.is_complex():
+        raise ValueError("complex multipliers / filters are not supported (fp32 only)")
+    K = mult.shape[2]
+    if filt.shape[2] != K:
+        raise ValueError(f"filters hold K = {filt.shape[2]} kernels, multipliers K = {K}")
+    if K < 1:
+        raise ValueError("at least one filter / multiplier pair is needed (K >= 1)")
+    if tuple(mult.shape[-2:]) != tuple(size):
+        raise ValueError(f"multipliers of spatial size {tuple(mult.shape[-2:])} do not match the image size {tuple(size)}")
+    for name, t in (("multipliers", mult), ("filters", filt)):
+        if t.shape[0] not in (1, B) or t.shape[1] not in (1, C):
+            raise ValueError(f"{name} of shape {tuple(t.shape)} do not broadcast to batch {B}, channels {C}")
+    d = ConvDesc(B, C, *size, filt.shape[0], filt.shape[1], *filt.shape[-2:], pad_mode(padding), 1)
+    ho, wo = ctypes.c_int32(), ctypes.c_int32()
+    check(_l().dinv_conv2d_out_size(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)))
+    return d, K, (ho.value, wo.value)
+
+
+def _pconv_fwd(x, mult, filt, padding):
+    dev = require_hip(x, mult, filt)
+    x, mult, filt = f32c(x), f32c(mult), f32c(filt)
+    B, C, H, W = x.shape
+    d, K, out = _pconv_desc(B, C, (H, W), mult, filt, padding)
+    y = torch.empty((B, C, *out), device=dev, dtype=torch.float32)
+    check(_l().dinv_pconv2d(ctypes.byref(d), K, mult.shape[0], mult.shape[1], ptr(x), ptr(mult), ptr(filt), ptr(y), stream_ptr(dev)))
+    return y
+
+
+def _pconv_adj(y, mult, filt, padding):
+    dev = require_hip(y, mult, filt)
+    y, mult, filt = f32c(y), f32c(mult), f32c(filt)
+    B, C = y.shape[:2]
+    size = tuple(mult.shape[-2:])
+    d, K, out = _pconv_desc(B, C, size, mult, filt, padding)
+    if out != tuple(y.shape[2:]):
+        raise ValueError(f"measurement of spatial size {tuple(y.shape[2:])} does not match the operator output {out}")
+    x = torch.empty((B, C, *size), device=dev, dtype=torch.float32)
+    check(_l().dinv_pconv2d_transpose(ctypes.byref(d), K, mult.shape[0], mult.shape[1], ptr(y), ptr(mult), ptr(filt), ptr(x),
+                                      stream_ptr(dev)))
+    return x
+
+
+class _PConv(torch.autograd.Function):
+    """x -> sum_k conv(w_k x, h_k) in one launch; differentiable in x (parameters that record a gradient take the composition)"""
+
+    @staticmethod
+    def forward(x, mult, filt, padding):
+        return _pconv_fwd(x, mult, filt, padding)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _, mult, filt, padding = inputs
+        ctx.save_for_backward(mult, filt)
+        ctx.padding = padding
+
+    @staticmethod
+    def backward(ctx, g):
+        mult, filt = ctx.saved_tensors
+        return (_PConvT.apply(g, mult, filt, ctx.padding) if ctx.needs_input_grad[0] else None), None, None, None
+
+
+class _PConvT(torch.autograd.Function):
+    @staticmethod
+    def forward(y, mult, filt, padding):
+        return _pconv_adj(y, mult, filt, padding)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _, mult, filt, padding = inputs
+        ctx.save_for_backward(mult, filt)
+        ctx.padding = padding
+
+    @staticmethod
+    def backward(ctx, g):
+        mult, filt = ctx.saved_tensors
+        return (_PConv.apply(g, mult, filt, ctx.padding) if ctx.needs_input_grad[0] else None), None, None, None
+
+
+def _records_grad(*tensors):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def product_conv2d(x, mult, filt, padding="valid"):
+    """sum_k conv2d(w_k x, h_k): one launch of dinv_pconv2d; when the multipliers or the filters record a gradient, the composition
+    of the differentiable pieces (torch multiply, _Conv, sum over k), whose filter gradient is dinv_conv2d_filter_grad"""
+    if not _records_grad(mult, filt):
+        return _PConv.apply(x, mult, filt, padding)
+    _pconv_desc(x.shape[0], x.shape[1], tuple(x.shape[2:]), mult, filt, padding)
+    out = None
+    for k in range(mult.shape[2]):
+        t = _Conv.apply(mult[:, :, k] * x, filt[:, :, k], padding, 1)
+        out = t if out is None else out + t
+    return out
+
+
+def product_conv2d_transpose(y, mult, filt, padding="valid"):
+    """sum_k w_k conv2d_transpose(y, h_k): one launch of dinv_pconv2d_transpose, or the composition as in product_conv2d"""
+    if not _records_grad(mult, filt):
+        return _PConvT.apply(y, mult, filt, padding)
+    size = tuple(mult.shape[-2:])
+    _pconv_desc(y.shape[0], y.shape[1], size, mult, filt, padding)
+    out = None
+    for k in range(mult.shape[2]):
+        t = mult[:, :, k] * _ConvT.apply(y, filt[:, :, k], padding, 1, size)
+        out = t if out is None else out + t
+    return out
 
 
 # --------------------------------------------------------------------------- rfft2 / irfft2

@@ -3,7 +3,7 @@ from .forward import (Physics, LinearPhysics, DecomposablePhysics, Denoising, ad
 from .noise import NoiseModel, ZeroNoise, GaussianNoise, PoissonNoise, PoissonGaussianNoise, LogPoissonNoise
 from .mri import MRI, MultiCoilMRI, MRIMixin
 from .tomography import Tomography, RampFilter
-from .blur import Blur, BlurFFT, Downsampling
+from .blur import Blur, BlurFFT, Downsampling, SpaceVaryingBlur
 from .singlepixel import SinglePixelCamera
 from .compressed_sensing import CompressedSensing
 from .structured_random import StructuredRandom

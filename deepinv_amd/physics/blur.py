@@ -1,6 +1,6 @@
-"""``Blur``, ``BlurFFT`` and ``Downsampling`` on HIP kernels — API mirror of
-deepinv/physics/blur.py:15-389 (Downsampling), :443-561 (Blur), :564-737 (BlurFFT).
-Buffer names (``filter``, ``mask``, ``angle``, ``Fh``, ``Fhc``, ``Fh2``) follow the reference.
+"""``Blur``, ``BlurFFT``, ``Downsampling`` and ``SpaceVaryingBlur`` on HIP kernels — API mirror of
+deepinv/physics/blur.py:15-389 (Downsampling), :443-561 (Blur), :564-737 (BlurFFT), :740-868 (SpaceVaryingBlur).
+Buffer names (``filter``, ``mask``, ``angle``, ``Fh``, ``Fhc``, ``Fh2``, ``filters``, ``multipliers``) follow the reference.
 """
 from __future__ import annotations
 
@@ -334,3 +334,46 @@ class Downsampling(LinearPhysics):
         S = hfft.fftn(r.to(torch.complex64), dim=(-2, -1), norm="backward") / (self._alias_mean + 1 / gamma)
         s = torch.real(hfft.ifftn(S, dim=(-2, -1), norm="backward"))
         return z + self.A_adjoint(s.contiguous())
+
+
+class SpaceVaryingBlur(LinearPhysics):
+    r"""Space-varying blur as a product convolution ``y = sum_k h_k * (w_k . x)`` with filters ``h`` (b, c, K, h, w) and
+    multipliers ``w`` (b, c, K, H, W), b in {1, B} and c in {1, C} independently (blur.py:740-868).  ``A`` and ``A_adjoint`` are
+    one kernel launch each (csrc/blur.hip: the loop over k runs inside the kernel); 2-D only."""
+
+    def __init__(self, filters: Tensor = None, multipliers: Tensor = None, padding: str = "valid", use_fft: bool = False,
+                 device=torch.device("cpu"), **kwargs):
+        super().__init__(device=device, **kwargs)
+        for name, t in (("filters", filters), ("multipliers", multipliers)):
+            assert isinstance(t, Tensor) or t is None, f"The {name} must be a torch.Tensor or None, got {type(t)}."
+        self.register_buffer("filters", filters)
+        self.register_buffer("multipliers", multipliers)
+        self.padding = padding
+        self.use_fft = use_fft
+        self.to(device)
+
+    def _ready(self, x):
+        if x.dim() != 4:
+            raise ValueError(f"SpaceVaryingBlur is 2-D only: expected a 4D tensor (B, C, H, W), got {x.dim()}D")
+        if not isinstance(self.filters, Tensor) or not isinstance(self.multipliers, Tensor):
+            raise ValueError("SpaceVaryingBlur needs both `filters` and `multipliers`")
+
+    def A(self, x: Tensor, filters: Tensor = None, multipliers: Tensor = None, padding: str = None, **kwargs) -> Tensor:
+        self.update_parameters(filters=filters, multipliers=multipliers, padding=padding, **kwargs)
+        self._ready(x)
+        return dF.product_convolution2d(x, self.multipliers, self.filters, self.padding, use_fft=self.use_fft)
+
+    def A_adjoint(self, y: Tensor, filters: Tensor = None, multipliers: Tensor = None, padding: str = None, **kwargs) -> Tensor:
+        """the image size is that of the multipliers"""
+        self.update_parameters(filters=filters, multipliers=multipliers, padding=padding, **kwargs)
+        self._ready(y)
+        return dF.product_convolution2d_adjoint(y, self.multipliers, self.filters, self.padding, use_fft=self.use_fft)
+
+    def update_parameters(self, filters: Tensor = None, multipliers: Tensor = None, padding: str = None, **kwargs):
+        if padding is not None:
+            hc.pad_mode(padding)
+            self.padding = padding
+        for name, t in (("filters", filters), ("multipliers", multipliers)):
+            if isinstance(t, Tensor) and getattr(self, name) is None:
+                setattr(self, name, t.to(self._device_holder.device))   # buffer was registered as None: install the tensor
+        super().update_parameters(filters=filters, multipliers=multipliers, **kwargs)

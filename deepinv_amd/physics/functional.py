@@ -1,5 +1,6 @@
 """Functional layer of the blur operators — API mirror of ``deepinv.physics.functional``
 (convolution.py: conv2d / conv_transpose2d / conv2d_fft / conv_transpose2d_fft / filter_fft;
+product_convolution.py: product_convolution2d / product_convolution2d_adjoint; multiplier.py: multiplier / multiplier_adjoint;
 blur.py: gaussian_blur / bilinear_filter / bicubic_filter / sinc_filter / kaiser_window).
 
 The convolutions run on the HIP kernels of csrc/blur.hip; the filter constructors are tiny
@@ -150,6 +151,66 @@ def _fold_padding(x, padding, p, i):
             raise ValueError(f"padding = '{padding}' not implemented.")
         x = core
     return x
+
+
+# --------------------------------------------------------------------------- product convolution (SpaceVaryingBlur)
+def _check_multiplier(x, mult):
+    if x.dim() != mult.dim():
+        raise ValueError("Input and filter must have the same number of dimension")
+    if mult.is_complex():
+        raise ValueError("complex multipliers are not supported (fp32 only)")
+    hc.require_hip(x, mult)
+
+
+def multiplier(x, mult):
+    """``mult * x`` with ``mult`` of size (b, c, ...), b in {1, B}, c in {1, C} (functional/multiplier.py:5-20)."""
+    _check_multiplier(x, mult)
+    return mult * x
+
+
+def multiplier_adjoint(x, mult):
+    """Adjoint of :func:`multiplier` (functional/multiplier.py:23-39); real multipliers: the same product, per plane - a
+    broadcast dimension is not reduced."""
+    _check_multiplier(x, mult)
+    return mult * x
+
+
+def _check_pconv(x, w, h):
+    if x.dim() != 4:
+        raise ValueError(f"product convolution is 2-D only: expected a 4D image (B, C, H, W), got {x.dim()}D")
+    if w.dim() != 5 or h.dim() != 5:
+        raise ValueError(f"multipliers and filters must be 5D tensors (b, c, K, ., .), got {w.dim()}D and {h.dim()}D")
+    if w.is_complex() or h.is_complex():
+        raise ValueError("complex multipliers / filters are not supported (fp32 only)")
+    if w.shape[2] != h.shape[2]:
+        raise ValueError(f"filters hold K = {h.shape[2]} kernels, multipliers K = {w.shape[2]}")
+
+
+def product_convolution2d(x, w, h, padding="valid", use_fft=False):
+    r"""``y = sum_k h_k * (w_k . x)`` (functional/product_convolution.py:10-41) for x (B, C, H, W), multipliers w (b, c, K, H, W)
+    and filters h (b', c', K, fh, fw).  One launch of csrc/blur.hip; ``use_fft=True`` is the reference's loop over k on
+    :func:`conv2d_fft`."""
+    _check_pconv(x, w, h)
+    hc.pad_mode(padding)
+    if not use_fft:
+        return hc.product_conv2d(x, w, h, padding)
+    result = 0.0
+    for k in range(w.size(2)):
+        result = result + conv2d_fft(multiplier(x, w[:, :, k]), h[:, :, k].contiguous(), padding=padding)
+    return result
+
+
+def product_convolution2d_adjoint(y, w, h, padding="valid", use_fft=False):
+    r"""``x = sum_k w_k . (h_k *^T y)`` (functional/product_convolution.py:44-68), the exact transpose of
+    :func:`product_convolution2d`; the image size is that of the multipliers."""
+    _check_pconv(y, w, h)
+    hc.pad_mode(padding)
+    if not use_fft:
+        return hc.product_conv2d_transpose(y, w, h, padding)
+    result = 0.0
+    for k in range(w.size(2)):
+        result = result + multiplier_adjoint(conv_transpose2d_fft(y, h[:, :, k].contiguous(), padding=padding), w[:, :, k])
+    return result
 
 
 # --------------------------------------------------------------------------- volumes (convolution.py:333-640)

@@ -478,6 +478,18 @@ int dinv_conv2d_transpose(const dinv_conv_desc* d, const float* y, const float* 
  * dinv_conv2d_transpose. */
 int dinv_conv2d_filter_grad(const dinv_conv_desc* d, const float* x, const float* gy, float* dk_planes, dinv_stream_t stream);
 
+/* Product convolution (SpaceVaryingBlur.A, deepinv/physics/blur.py:740-868; product_convolution2d,
+ * functional/product_convolution.py:10-41): y = sum_{k<K} conv2d(w_k .* x, h_k) in ONE launch, no workspace - the k loop runs inside
+ * the kernel and the multiplication happens before the padding, as in the reference.  d->stride must be 1; d->fbatch / d->fchannels
+ * describe h [fb,fc,K,fh,fw]; w is [mbatch,mchannels,K,H,W] with mbatch in {1,B}, mchannels in {1,C}; y is [B,C,Ho,Wo] of
+ * dinv_conv2d_out_size. */
+int dinv_pconv2d(const dinv_conv_desc* d, int32_t K, int32_t mbatch, int32_t mchannels, const float* x, const float* w,
+                 const float* h, float* y, dinv_stream_t stream);
+/* exact transpose of dinv_pconv2d: x = sum_{k<K} w_k .* conv2d_transpose(y, h_k)   (SpaceVaryingBlur.A_adjoint;
+ * product_convolution2d_adjoint, product_convolution.py:44-68; multiplier_adjoint, functional/multiplier.py:23-39), one launch */
+int dinv_pconv2d_transpose(const dinv_conv_desc* d, int32_t K, int32_t mbatch, int32_t mchannels, const float* y, const float* w,
+                           const float* h, float* x, dinv_stream_t stream);
+
 /* The same three operators on volumes [B,C,D,H,W] with filters [fb,fc,fd,fh,fw] (conv3d / conv_transpose3d, convolution.py:333-452;
  * Blur on 5-D tensors, blur.py:535-561): the 2-D padding rule on every axis, stride 1. */
 typedef struct {
