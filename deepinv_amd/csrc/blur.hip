@@ -48,29 +48,41 @@ __device__ __forceinline__ int pad_map(int q, int n, int mode) {
     }
 }
 
+// plane of a filter or multiplier stack [nb in {1,B}, nc in {1,C}, ...] that image plane (b, c) uses: an axis of extent 1 is broadcast
+__device__ __forceinline__ int64_t plane_index(int b, int c, int nb, int nc) { return (int64_t)(nb > 1 ? b : 0) * nc + (nc > 1 ? c : 0); }
+
+// the n taps of one filter into LDS in reverse order (true convolution: kf[u,v] = k[h-1-u, w-1-v]); by the 256 threads of a workgroup
+__device__ __forceinline__ void load_flipped(float* __restrict__ ks, const float* __restrict__ kf, int n) {
+    for (int i = threadIdx.x; i < n; i += 256) ks[i] = kf[n - 1 - i];
+}
+
+// the (u, v) tap loop of ONE output (io, jo) of the padded true convolution at stride s, joined to `acc`: ks the flipped filter,
+// value_at(r, cc) the source value at unpadded (r, cc)
+template <class F>
+__device__ __forceinline__ float pad_taps(const ConvGeom& g, const float* ks, int io, int jo, int s, float acc, F value_at) {
+    for (int u = 0; u < g.h; ++u) {
+        const int r = pad_map(io * s + u - g.pt, g.H, g.mode);
+        if (r < 0) continue;
+        for (int v = 0; v < g.w; ++v) {
+            const int cc = pad_map(jo * s + v - g.pl, g.W, g.mode);
+            if (cc >= 0) acc = fmaf(ks[u * g.w + v], value_at(r, cc), acc);
+        }
+    }
+    return acc;
+}
+
 // y[b,c,io,jo] = sum_{u,v} kf[u,v] * xpad[io*s+u, jo*s+v],  kf[u,v] = k[h-1-u, w-1-v]
 __global__ __launch_bounds__(256) void conv2d_pad_kernel(ConvGeom g, const float* __restrict__ x,
                                                          const float* __restrict__ k, float* __restrict__ y) {
     DINV_DYN_LDS(float, ks);  // flipped filter of this (b,c)
     const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
-    const float* kf = k + ((int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0)) * g.h * g.w;
-    for (int i = threadIdx.x; i < g.h * g.w; i += 256) ks[i] = kf[g.h * g.w - 1 - i];
+    load_flipped(ks, k + plane_index(b, c, g.fb, g.fc) * g.h * g.w, g.h * g.w);
     __syncthreads();
     const int jo = blockIdx.x * 64 + (threadIdx.x & 63);
     const int io = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (io >= g.Ho || jo >= g.Wo) return;
     const float* img = x + (int64_t)bc * g.H * g.W;
-    float acc = 0.f;
-    for (int u = 0; u < g.h; ++u) {
-        const int r = pad_map(io * g.stride + u - g.pt, g.H, g.mode);
-        if (r < 0) continue;
-        const float* row = img + (int64_t)r * g.W;
-        for (int v = 0; v < g.w; ++v) {
-            const int cc = pad_map(jo * g.stride + v - g.pl, g.W, g.mode);
-            if (cc >= 0) acc = fmaf(ks[u * g.w + v], row[cc], acc);
-        }
-    }
-    y[((int64_t)bc * g.Ho + io) * g.Wo + jo] = acc;
+    y[((int64_t)bc * g.Ho + io) * g.Wo + jo] = pad_taps(g, ks, io, jo, g.stride, 0.f, [&](int r, int cc) { return img[(int64_t)r * g.W + cc]; });
 }
 
 // ---- LDS-tiled form for stride 1 (Blur.A with every padding mode; Blur.A_adjoint for valid / circular / constant, whose transpose
@@ -145,44 +157,55 @@ __device__ __forceinline__ void tile_chunk(f32x2 (&acc)[4][2], const float* __re
     }
 }
 
-__global__ __launch_bounds__(256) void conv2d_tiled_kernel(TileConv g, const float* __restrict__ in, const float* __restrict__ k,
-                                                           float* __restrict__ out) {
-    DINV_DYN_LDS(float, smem);
-    const int w4 = (g.w + 3) & ~3, ph = 64 + g.h - 1;
-    float* kt = smem;                                   // [(h + 6)][w4]: rows -3 .. h + 2 of the (flipped) filter, zero outside
-    float* patch = smem + (g.h + 6) * w4;               // [ph][pitch]
-    const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
-    const float* kf = k + ((int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0)) * g.h * g.w;
-    const int tid = threadIdx.x;
-    for (int i = tid; i < (g.h + 6) * w4; i += 256) {
+// rows -3 .. h + 2 of one filter as the table tile_chunk walks ([(h + 6)][w4], zero outside the filter), flipped or not
+__device__ __forceinline__ void tile_load_taps(float* __restrict__ kt, const float* __restrict__ kf, int h, int w, int w4, int flip, int tid) {
+    for (int i = tid; i < (h + 6) * w4; i += 256) {
         const int u = i / w4 - 3, v = i - (u + 3) * w4;
         float t = 0.f;
-        if (u >= 0 && u < g.h && v < g.w) t = g.flip ? kf[g.h * g.w - 1 - (u * g.w + v)] : kf[u * g.w + v];
+        if (u >= 0 && u < h && v < w) t = flip ? kf[h * w - 1 - (u * w + v)] : kf[u * w + v];
         kt[i] = t;
     }
-    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
-    const float* img = in + (int64_t)bc * g.Hi * g.Wi;
+}
+
+// the (64 + h - 1) x pw input patch of the tile at (r0, c0), every element through pad_map once: value_at(at) is the source value at
+// offset `at` of the input plane, zero where the map has no source
+template <class F>
+__device__ __forceinline__ void tile_stage_patch(float* __restrict__ patch, const TileConv& g, int r0, int c0, int tid, F value_at) {
+    const int ph = 64 + g.h - 1;
     for (int pr = tid / 64; pr < ph; pr += 4) {
         const int rr = pad_map(r0 + pr - g.off_r, g.Hi, g.mode);
         const bool rok = rr >= 0 && rr < g.Hi;
         for (int pc = tid & 63; pc < g.pw; pc += 64) {
             const int cc = pad_map(c0 + pc - g.off_c, g.Wi, g.mode);
-            patch[pr * g.pitch + pc] = (rok && cc >= 0 && cc < g.Wi) ? img[(int64_t)rr * g.Wi + cc] : 0.f;
+            patch[pr * g.pitch + pc] = (rok && cc >= 0 && cc < g.Wi) ? value_at((int64_t)rr * g.Wi + cc) : 0.f;
         }
     }
-    __syncthreads();
-    const int tx = tid & 15, ty = tid >> 4;
-    f32x2 acc[4][2];
+}
+
+__device__ __forceinline__ void tile_zero(f32x2 (&acc)[4][2]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) { acc[i][0] = f32x2{0.f, 0.f}; acc[i][1] = f32x2{0.f, 0.f}; }
-    const float* pbase = patch + (ty * 4) * g.pitch + tx * 4;
-    const float* kbase = kt + 3 * w4;
-    const int nfull = g.w >> 2, rem = g.w & 3;
-    for (int q = 0; q < nfull; ++q) tile_chunk<4>(acc, pbase + 4 * q, kbase + 4 * q, g.pitch, w4, g.h);
-    if (rem == 1) tile_chunk<1>(acc, pbase + 4 * nfull, kbase + 4 * nfull, g.pitch, w4, g.h);
-    else if (rem == 2) tile_chunk<2>(acc, pbase + 4 * nfull, kbase + 4 * nfull, g.pitch, w4, g.h);
-    else if (rem == 3) tile_chunk<3>(acc, pbase + 4 * nfull, kbase + 4 * nfull, g.pitch, w4, g.h);
-    float* o = out + (int64_t)bc * g.Ho * g.Wo;
+}
+
+// every chunk of four filter columns of one filter over the thread's 4 x 4 outputs
+__device__ __forceinline__ void tile_filter(f32x2 (&acc)[4][2], const float* __restrict__ pbase, const float* __restrict__ kbase, int pitch,
+                                            int w4, int h, int w) {
+    const int nfull = w >> 2, rem = w & 3;
+    for (int q = 0; q < nfull; ++q) tile_chunk<4>(acc, pbase + 4 * q, kbase + 4 * q, pitch, w4, h);
+    if (rem == 1) tile_chunk<1>(acc, pbase + 4 * nfull, kbase + 4 * nfull, pitch, w4, h);
+    else if (rem == 2) tile_chunk<2>(acc, pbase + 4 * nfull, kbase + 4 * nfull, pitch, w4, h);
+    else if (rem == 3) tile_chunk<3>(acc, pbase + 4 * nfull, kbase + 4 * nfull, pitch, w4, h);
+}
+
+// the column pairs of the accumulators as the thread's 4 x 4 outputs
+__device__ __forceinline__ void tile_unpack(const f32x2 (&acc)[4][2], float (&res)[4][4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { res[i][0] = acc[i][0].x; res[i][1] = acc[i][0].y; res[i][2] = acc[i][1].x; res[i][3] = acc[i][1].y; }
+}
+
+// the thread's 4 x 4 outputs to plane `o`: 16-byte stores where the row allows, scalar ones at a ragged edge
+__device__ __forceinline__ void tile_store(const TileConv& g, const float* out, float* __restrict__ o, int r0, int c0, int tx, int ty,
+                                           const float (&res)[4][4]) {
     const int oc = c0 + tx * 4;
     const bool vec = (g.Wo % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0) && (((int64_t)g.Ho * g.Wo) % 4 == 0);
 #pragma unroll
@@ -190,15 +213,35 @@ __global__ __launch_bounds__(256) void conv2d_tiled_kernel(TileConv g, const flo
         const int orow = r0 + ty * 4 + i;
         if (orow >= g.Ho) continue;
         float* dst = o + (int64_t)orow * g.Wo + oc;
-        const float v4[4] = {acc[i][0].x, acc[i][0].y, acc[i][1].x, acc[i][1].y};
         if (vec && oc + 3 < g.Wo) {
-            *reinterpret_cast<float4*>(dst) = make_float4(v4[0], v4[1], v4[2], v4[3]);
+            *reinterpret_cast<float4*>(dst) = make_float4(res[i][0], res[i][1], res[i][2], res[i][3]);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (oc + j < g.Wo) dst[j] = v4[j];
+                if (oc + j < g.Wo) dst[j] = res[i][j];
         }
     }
+}
+
+__global__ __launch_bounds__(256) void conv2d_tiled_kernel(TileConv g, const float* __restrict__ in, const float* __restrict__ k,
+                                                           float* __restrict__ out) {
+    DINV_DYN_LDS(float, smem);
+    const int w4 = (g.w + 3) & ~3;
+    float* kt = smem;                                   // [(h + 6)][w4]: rows -3 .. h + 2 of the (flipped) filter, zero outside
+    float* patch = smem + (g.h + 6) * w4;               // [64 + h - 1][pitch]
+    const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+    const float* img = in + (int64_t)bc * g.Hi * g.Wi;
+    tile_load_taps(kt, k + plane_index(b, c, g.fb, g.fc) * g.h * g.w, g.h, g.w, w4, g.flip, tid);
+    tile_stage_patch(patch, g, r0, c0, tid, [&](int64_t at) { return img[at]; });
+    __syncthreads();
+    f32x2 acc[4][2];
+    tile_zero(acc);
+    tile_filter(acc, patch + (ty * 4) * g.pitch + tx * 4, kt + 3 * w4, g.pitch, w4, g.h, g.w);
+    float res[4][4];
+    tile_unpack(acc, res);
+    tile_store(g, out, out + (int64_t)bc * g.Ho * g.Wo, r0, c0, tx, ty, res);
 }
 
 // pre-images of unpadded index t under pad_map, in padded coordinates [0, n+pt+pb): up to 3 ranges [lo,hi]
@@ -230,8 +273,7 @@ __global__ __launch_bounds__(256) void conv2d_pad_transpose_kernel(ConvGeom g, c
                                                                    float* __restrict__ x) {
     DINV_DYN_LDS(float, ks);
     const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
-    const float* kf = k + ((int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0)) * g.h * g.w;
-    for (int i = threadIdx.x; i < g.h * g.w; i += 256) ks[i] = kf[g.h * g.w - 1 - i];
+    load_flipped(ks, k + plane_index(b, c, g.fb, g.fc) * g.h * g.w, g.h * g.w);
     __syncthreads();
     const int cc = blockIdx.x * 64 + (threadIdx.x & 63);
     const int r = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -322,26 +364,35 @@ int make_geom(const dinv_conv_desc* d, ConvGeom* g) {
     return 0;
 }
 
-// the LDS-tiled kernel for a stride-1 geometry; returns 1 when it took the call, 0 when the caller's general kernel must
-inline int launch_tiled(const ConvGeom& g, bool transpose, const float* in, const float* k, float* out, hipStream_t s, int* took) {
-    *took = 0;
-    if (g.stride != 1) return 0;
-    if (transpose && !(g.mode == PAD_VALID || g.mode == PAD_CIRCULAR || g.mode == PAD_CONSTANT)) return 0;
-    TileConv t;
-    t.C = g.C; t.fb = g.fb; t.fc = g.fc; t.h = g.h; t.w = g.w;
+// THE rule of the tiled kernels (conv2d_tiled_kernel and the two pconv2d_tiled ones) for a stride-1 geometry, and their set-up: true
+// with the kernel's geometry and its dynamic LDS when the tiled form takes the call - every forward, the transpose where it is again
+// a gather with an index map (valid / circular / constant), and the filter table plus the patch within 64 KB of LDS; on false
+// *t is left alone
+bool make_tile(const ConvGeom& g, bool transpose, TileConv* t, size_t* lds) {
+    if (transpose && !(g.mode == PAD_VALID || g.mode == PAD_CIRCULAR || g.mode == PAD_CONSTANT)) return false;
+    const int w4 = (g.w + 3) & ~3, pw = 64 + w4;        // patch columns; the LDS row pitch is the same
+    *lds = ((size_t)(g.h + 6) * w4 + (size_t)(64 + g.h - 1) * pw) * sizeof(float);
+    if (*lds > 64 * 1024) return false;
+    t->C = g.C; t->fb = g.fb; t->fc = g.fc; t->h = g.h; t->w = g.w;
     if (!transpose) {
-        t.Hi = g.H; t.Wi = g.W; t.Ho = g.Ho; t.Wo = g.Wo; t.off_r = g.pt; t.off_c = g.pl; t.mode = g.mode; t.flip = 1;
+        t->Hi = g.H; t->Wi = g.W; t->Ho = g.Ho; t->Wo = g.Wo; t->off_r = g.pt; t->off_c = g.pl; t->mode = g.mode; t->flip = 1;
     } else {
         // x[r, c] = sum_{u, v} kf[u, v] y[r + pt - u, c + pl - v]: with u' = h - 1 - u a gather with the UNFLIPPED filter
         // (zero outside y for valid / constant, periodic for circular)
-        t.Hi = g.Ho; t.Wi = g.Wo; t.Ho = g.H; t.Wo = g.W; t.off_r = g.h - 1 - g.pt; t.off_c = g.w - 1 - g.pl;
-        t.mode = g.mode == PAD_CIRCULAR ? PAD_CIRCULAR : PAD_CONSTANT; t.flip = 0;
+        t->Hi = g.Ho; t->Wi = g.Wo; t->Ho = g.H; t->Wo = g.W; t->off_r = g.h - 1 - g.pt; t->off_c = g.w - 1 - g.pl;
+        t->mode = g.mode == PAD_CIRCULAR ? PAD_CIRCULAR : PAD_CONSTANT; t->flip = 0;
     }
-    const int w4 = (g.w + 3) & ~3;
-    t.pw = 64 + w4;
-    t.pitch = t.pw;
-    const size_t lds = ((size_t)(g.h + 6) * w4 + (size_t)(64 + g.h - 1) * t.pitch) * sizeof(float);
-    if (lds > 64 * 1024) return 0;
+    t->pw = pw;
+    t->pitch = pw;
+    return true;
+}
+
+// the LDS-tiled kernel for a stride-1 geometry; returns 1 when it took the call, 0 when the caller's general kernel must
+inline int launch_tiled(const ConvGeom& g, bool transpose, const float* in, const float* k, float* out, hipStream_t s, int* took) {
+    *took = 0;
+    TileConv t;
+    size_t lds;
+    if (g.stride != 1 || !make_tile(g, transpose, &t, &lds)) return 0;
     hipLaunchKernelGGL(conv2d_tiled_kernel, dim3((t.Wo + 63) / 64, (t.Ho + 63) / 64, g.B * g.C), dim3(256), lds, s, t, in, k, out);
     DINV_CHECK_LAUNCH();
     *took = 1;
@@ -355,114 +406,52 @@ inline int launch_tiled(const ConvGeom& g, bool transpose, const float* in, cons
 // the K-fold intermediate never exists: x (or y), every multiplier once and the result cross memory, (K + 2) H W words.
 struct ProdConv { int32_t K, mb, mc; };
 
-// rows -3 .. h + 2 of one filter as the table tile_chunk walks ([(h + 6)][w4], zero outside the filter), flipped or not
-__device__ __forceinline__ void tile_load_taps(float* __restrict__ kt, const float* __restrict__ kf, int h, int w, int w4, int flip, int tid) {
-    for (int i = tid; i < (h + 6) * w4; i += 256) {
-        const int u = i / w4 - 3, v = i - (u + 3) * w4;
-        float t = 0.f;
-        if (u >= 0 && u < h && v < w) t = flip ? kf[h * w - 1 - (u * w + v)] : kf[u * w + v];
-        kt[i] = t;
-    }
-}
-
-// every chunk of four filter columns of one filter over the thread's 4 x 4 outputs
-__device__ __forceinline__ void tile_filter(f32x2 (&acc)[4][2], const float* __restrict__ pbase, const float* __restrict__ kbase, int pitch,
-                                            int w4, int h, int w) {
-    const int nfull = w >> 2, rem = w & 3;
-    for (int q = 0; q < nfull; ++q) tile_chunk<4>(acc, pbase + 4 * q, kbase + 4 * q, pitch, w4, h);
-    if (rem == 1) tile_chunk<1>(acc, pbase + 4 * nfull, kbase + 4 * nfull, pitch, w4, h);
-    else if (rem == 2) tile_chunk<2>(acc, pbase + 4 * nfull, kbase + 4 * nfull, pitch, w4, h);
-    else if (rem == 3) tile_chunk<3>(acc, pbase + 4 * nfull, kbase + 4 * nfull, pitch, w4, h);
-}
-
-// the thread's 4 x 4 outputs to plane `o`: 16-byte stores where the row allows, scalar ones at a ragged edge
-__device__ __forceinline__ void tile_store(const TileConv& g, const float* out, float* __restrict__ o, int r0, int c0, int tx, int ty,
-                                           const float (&res)[4][4]) {
-    const int oc = c0 + tx * 4;
-    const bool vec = (g.Wo % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0) && (((int64_t)g.Ho * g.Wo) % 4 == 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int orow = r0 + ty * 4 + i;
-        if (orow >= g.Ho) continue;
-        float* dst = o + (int64_t)orow * g.Wo + oc;
-        if (vec && oc + 3 < g.Wo) {
-            *reinterpret_cast<float4*>(dst) = make_float4(res[i][0], res[i][1], res[i][2], res[i][3]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (oc + j < g.Wo) dst[j] = res[i][j];
-        }
-    }
-}
-
 // forward, tiled: per k the staged patch is x[m(p)] w_k[m(p)] (the product BEFORE the padding, m = pad_map) and the filter table is
 // h_k flipped; the 4 x 4 accumulators stay in registers across k, so an output is ONE chain of K h w multiply-adds
 __global__ __launch_bounds__(256) void pconv2d_tiled_kernel(TileConv g, ProdConv p, const float* __restrict__ in,
                                                             const float* __restrict__ mult, const float* __restrict__ k,
                                                             float* __restrict__ out) {
     DINV_DYN_LDS(float, smem);
-    const int w4 = (g.w + 3) & ~3, ph = 64 + g.h - 1;
+    const int w4 = (g.w + 3) & ~3;
     float* kt = smem;                                   // [(h + 6)][w4]
-    float* patch = smem + (g.h + 6) * w4;               // [ph][pitch]
+    float* patch = smem + (g.h + 6) * w4;               // [64 + h - 1][pitch]
     const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
-    const int64_t fplane = (int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0);
-    const int64_t mplane = (int64_t)(p.mb > 1 ? b : 0) * p.mc + (p.mc > 1 ? c : 0);
+    const int64_t fplane = plane_index(b, c, g.fb, g.fc), mplane = plane_index(b, c, p.mb, p.mc);
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
     const float* img = in + (int64_t)bc * g.Hi * g.Wi;
     f32x2 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { acc[i][0] = f32x2{0.f, 0.f}; acc[i][1] = f32x2{0.f, 0.f}; }
+    tile_zero(acc);
     const float* pbase = patch + (ty * 4) * g.pitch + tx * 4;
     for (int kk = 0; kk < p.K; ++kk) {
         const float* wk = mult + (mplane * p.K + kk) * (int64_t)g.Hi * g.Wi;
         if (kk) __syncthreads();                        // the previous filter's walk has left the table and the patch
         tile_load_taps(kt, k + (fplane * p.K + kk) * g.h * g.w, g.h, g.w, w4, 1, tid);
-        for (int pr = tid / 64; pr < ph; pr += 4) {
-            const int rr = pad_map(r0 + pr - g.off_r, g.Hi, g.mode);
-            const bool rok = rr >= 0 && rr < g.Hi;
-            for (int pc = tid & 63; pc < g.pw; pc += 64) {
-                const int cc = pad_map(c0 + pc - g.off_c, g.Wi, g.mode);
-                float v = 0.f;
-                if (rok && cc >= 0 && cc < g.Wi) {
-                    const int64_t at = (int64_t)rr * g.Wi + cc;
-                    v = img[at] * wk[at];
-                }
-                patch[pr * g.pitch + pc] = v;
-            }
-        }
+        tile_stage_patch(patch, g, r0, c0, tid, [&](int64_t at) { return img[at] * wk[at]; });
         __syncthreads();
         tile_filter(acc, pbase, kt + 3 * w4, g.pitch, w4, g.h, g.w);
     }
-    const float res[4][4] = {{acc[0][0].x, acc[0][0].y, acc[0][1].x, acc[0][1].y}, {acc[1][0].x, acc[1][0].y, acc[1][1].x, acc[1][1].y},
-                             {acc[2][0].x, acc[2][0].y, acc[2][1].x, acc[2][1].y}, {acc[3][0].x, acc[3][0].y, acc[3][1].x, acc[3][1].y}};
+    float res[4][4];
+    tile_unpack(acc, res);
     tile_store(g, out, out + (int64_t)bc * g.Ho * g.Wo, r0, c0, tx, ty, res);
 }
 
-// transposed, tiled (valid / circular / constant: a gather with an index map, see launch_tiled): the y patch does not depend on k and
+// transposed, tiled (valid / circular / constant: a gather with an index map, see make_tile): the y patch does not depend on k and
 // is staged once; every k re-walks it with its own unflipped table into fresh accumulators, and the partial result joins the total
 // with one multiply-add by w_k[r, c]
 __global__ __launch_bounds__(256) void pconv2d_tiled_transpose_kernel(TileConv g, ProdConv p, const float* __restrict__ in,
                                                                       const float* __restrict__ mult, const float* __restrict__ k,
                                                                       float* __restrict__ out) {
     DINV_DYN_LDS(float, smem);
-    const int w4 = (g.w + 3) & ~3, ph = 64 + g.h - 1;
+    const int w4 = (g.w + 3) & ~3;
     float* kt = smem;
     float* patch = smem + (g.h + 6) * w4;
     const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
-    const int64_t fplane = (int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0);
-    const int64_t mplane = (int64_t)(p.mb > 1 ? b : 0) * p.mc + (p.mc > 1 ? c : 0);
+    const int64_t fplane = plane_index(b, c, g.fb, g.fc), mplane = plane_index(b, c, p.mb, p.mc);
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
     const float* img = in + (int64_t)bc * g.Hi * g.Wi;
-    for (int pr = tid / 64; pr < ph; pr += 4) {
-        const int rr = pad_map(r0 + pr - g.off_r, g.Hi, g.mode);
-        const bool rok = rr >= 0 && rr < g.Hi;
-        for (int pc = tid & 63; pc < g.pw; pc += 64) {
-            const int cc = pad_map(c0 + pc - g.off_c, g.Wi, g.mode);
-            patch[pr * g.pitch + pc] = (rok && cc >= 0 && cc < g.Wi) ? img[(int64_t)rr * g.Wi + cc] : 0.f;
-        }
-    }
+    tile_stage_patch(patch, g, r0, c0, tid, [&](int64_t at) { return img[at]; });
     float res[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -475,19 +464,19 @@ __global__ __launch_bounds__(256) void pconv2d_tiled_transpose_kernel(TileConv g
         tile_load_taps(kt, k + (fplane * p.K + kk) * g.h * g.w, g.h, g.w, w4, 0, tid);
         __syncthreads();                                // (the first one also publishes the patch)
         f32x2 acc[4][2];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { acc[i][0] = f32x2{0.f, 0.f}; acc[i][1] = f32x2{0.f, 0.f}; }
+        tile_zero(acc);
         tile_filter(acc, pbase, kt + 3 * w4, g.pitch, w4, g.h, g.w);
+        float part[4][4];
+        tile_unpack(acc, part);
         const float* wk = mult + (mplane * p.K + kk) * (int64_t)g.Ho * g.Wo;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int orow = r0 + ty * 4 + i;
             if (orow >= g.Ho) continue;
             const float* wrow = wk + (int64_t)orow * g.Wo + oc;
-            const float part[4] = {acc[i][0].x, acc[i][0].y, acc[i][1].x, acc[i][1].y};
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (oc + j < g.Wo) res[i][j] = fmaf(part[j], wrow[j], res[i][j]);
+                if (oc + j < g.Wo) res[i][j] = fmaf(part[i][j], wrow[j], res[i][j]);
         }
     }
     tile_store(g, out, out + (int64_t)bc * g.Ho * g.Wo, r0, c0, tx, ty, res);
@@ -498,33 +487,19 @@ __global__ __launch_bounds__(256) void pconv2d_pad_kernel(ConvGeom g, ProdConv p
                                                           const float* __restrict__ k, float* __restrict__ y) {
     DINV_DYN_LDS(float, ks);  // flipped filter k of this (b,c)
     const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
-    const int64_t fplane = (int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0);
-    const int64_t mplane = (int64_t)(p.mb > 1 ? b : 0) * p.mc + (p.mc > 1 ? c : 0);
+    const int64_t fplane = plane_index(b, c, g.fb, g.fc), mplane = plane_index(b, c, p.mb, p.mc);
     const int jo = blockIdx.x * 64 + (threadIdx.x & 63);
     const int io = blockIdx.y * 4 + (threadIdx.x >> 6);
     const bool live = io < g.Ho && jo < g.Wo;
     const float* img = x + (int64_t)bc * g.H * g.W;
     float acc = 0.f;
     for (int kk = 0; kk < p.K; ++kk) {
-        const float* kf = k + (fplane * p.K + kk) * g.h * g.w;
         const float* wk = mult + (mplane * p.K + kk) * (int64_t)g.H * g.W;
         if (kk) __syncthreads();
-        for (int i = threadIdx.x; i < g.h * g.w; i += 256) ks[i] = kf[g.h * g.w - 1 - i];
+        load_flipped(ks, k + (fplane * p.K + kk) * g.h * g.w, g.h * g.w);
         __syncthreads();
         if (!live) continue;
-        for (int u = 0; u < g.h; ++u) {
-            const int r = pad_map(io + u - g.pt, g.H, g.mode);
-            if (r < 0) continue;
-            const float* row = img + (int64_t)r * g.W;
-            const float* wrow = wk + (int64_t)r * g.W;
-            for (int v = 0; v < g.w; ++v) {
-                const int cc = pad_map(jo + v - g.pl, g.W, g.mode);
-                if (cc >= 0) {
-                    const float xw = row[cc] * wrow[cc];
-                    acc = fmaf(ks[u * g.w + v], xw, acc);
-                }
-            }
-        }
+        acc = pad_taps(g, ks, io, jo, 1, acc, [&](int r, int cc) { const int64_t at = (int64_t)r * g.W + cc; return img[at] * wk[at]; });
     }
     if (live) y[((int64_t)bc * g.Ho + io) * g.Wo + jo] = acc;
 }
@@ -536,8 +511,7 @@ __global__ __launch_bounds__(256) void pconv2d_pad_transpose_kernel(ConvGeom g, 
                                                                     float* __restrict__ x) {
     DINV_DYN_LDS(float, ks);
     const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
-    const int64_t fplane = (int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0);
-    const int64_t mplane = (int64_t)(p.mb > 1 ? b : 0) * p.mc + (p.mc > 1 ? c : 0);
+    const int64_t fplane = plane_index(b, c, g.fb, g.fc), mplane = plane_index(b, c, p.mb, p.mc);
     const int cc = blockIdx.x * 64 + (threadIdx.x & 63);
     const int r = blockIdx.y * 4 + (threadIdx.x >> 6);
     const bool live = r < g.H && cc < g.W;
@@ -546,9 +520,8 @@ __global__ __launch_bounds__(256) void pconv2d_pad_transpose_kernel(ConvGeom g, 
     const Pre pcol = preimages(cc, g.W, g.pl, g.pr, g.mode);
     float total = 0.f;
     for (int kk = 0; kk < p.K; ++kk) {
-        const float* kf = k + (fplane * p.K + kk) * g.h * g.w;
         if (kk) __syncthreads();
-        for (int i = threadIdx.x; i < g.h * g.w; i += 256) ks[i] = kf[g.h * g.w - 1 - i];
+        load_flipped(ks, k + (fplane * p.K + kk) * g.h * g.w, g.h * g.w);
         __syncthreads();
         if (!live) continue;
         float acc = 0.f;
@@ -573,25 +546,17 @@ __global__ __launch_bounds__(256) void pconv2d_pad_transpose_kernel(ConvGeom g, 
     if (live) x[((int64_t)bc * g.H + r) * g.W + cc] = total;
 }
 
-// one launch per call: the tiled kernels wherever launch_tiled takes the plain convolution (the same LDS need), the general ones else
+// one launch per call: the tiled kernels wherever make_tile takes the geometry (as for the plain convolution), the general ones else
 inline int launch_pconv(const ConvGeom& g, const ProdConv& p, bool transpose, const float* in, const float* mult, const float* k, float* out,
                         hipStream_t s) {
-    const bool gather = !transpose || g.mode == PAD_VALID || g.mode == PAD_CIRCULAR || g.mode == PAD_CONSTANT;
-    const int w4 = (g.w + 3) & ~3;
-    const size_t lds = ((size_t)(g.h + 6) * w4 + (size_t)(64 + g.h - 1) * (64 + w4)) * sizeof(float);
-    if (gather && lds <= 64 * 1024) {
-        TileConv t;
-        t.C = g.C; t.fb = g.fb; t.fc = g.fc; t.h = g.h; t.w = g.w;
-        t.pw = 64 + w4;
-        t.pitch = t.pw;
-        const dim3 grid(((transpose ? g.W : g.Wo) + 63) / 64, ((transpose ? g.H : g.Ho) + 63) / 64, g.B * g.C);
+    TileConv t;
+    size_t lds;
+    if (make_tile(g, transpose, &t, &lds)) {
+        const dim3 grid((t.Wo + 63) / 64, (t.Ho + 63) / 64, g.B * g.C);
         if (!transpose) {
-            t.Hi = g.H; t.Wi = g.W; t.Ho = g.Ho; t.Wo = g.Wo; t.off_r = g.pt; t.off_c = g.pl; t.mode = g.mode; t.flip = 1;
             if (lds > kDefaultLdsBytes) if (int e = raise_lds_cap<pconv2d_tiled_kernel>(64 * 1024)) return e;
             hipLaunchKernelGGL(pconv2d_tiled_kernel, grid, dim3(256), lds, s, t, p, in, mult, k, out);
-        } else {        // as launch_tiled: a gather of y with the unflipped filter, zero outside y or periodic
-            t.Hi = g.Ho; t.Wi = g.Wo; t.Ho = g.H; t.Wo = g.W; t.off_r = g.h - 1 - g.pt; t.off_c = g.w - 1 - g.pl;
-            t.mode = g.mode == PAD_CIRCULAR ? PAD_CIRCULAR : PAD_CONSTANT; t.flip = 0;
+        } else {
             if (lds > kDefaultLdsBytes) if (int e = raise_lds_cap<pconv2d_tiled_transpose_kernel>(64 * 1024)) return e;
             hipLaunchKernelGGL(pconv2d_tiled_transpose_kernel, grid, dim3(256), lds, s, t, p, in, mult, k, out);
         }
@@ -642,9 +607,8 @@ __global__ __launch_bounds__(256) void conv2d_strided_kernel(StrideConv g, const
     float* ks = smem;                      // flipped filter [h][w]
     float* patch = smem + g.h * g.w;       // [PH][pitch]; general form: a row = s phases of PWs columns (column j s + b at [b][j])
     const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
-    const float* kf = k + ((int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0)) * g.h * g.w;
     const int tid = threadIdx.x;
-    for (int i = tid; i < g.h * g.w; i += 256) ks[i] = kf[g.h * g.w - 1 - i];
+    load_flipped(ks, k + plane_index(b, c, g.fb, g.fc) * g.h * g.w, g.h * g.w);
     const int r0 = blockIdx.y * 16, c0 = blockIdx.x * 16;
     const float* img = in + (int64_t)bc * g.Hi * g.Wi;
     const int pwide = g.s * g.PWs;
@@ -707,9 +671,8 @@ __global__ __launch_bounds__(256) void conv2d_strided_transpose_kernel(StrideCon
     float* ks = smem;                      // flipped filter [h][w]
     float* yp = smem + g.h * g.w;          // [PH][pitch] measurements
     const int bc = blockIdx.z, b = bc / g.C, c = bc % g.C;
-    const float* kf = k + ((int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0)) * g.h * g.w;
     const int tid = threadIdx.x;
-    for (int i = tid; i < g.h * g.w; i += 256) ks[i] = kf[g.h * g.w - 1 - i];
+    load_flipped(ks, k + plane_index(b, c, g.fb, g.fc) * g.h * g.w, g.h * g.w);
     const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
     const int base_r = (r0 + g.pt) / g.s - (g.h - 1) / g.s, base_c = (c0 + g.pl) / g.s - (g.w - 1) / g.s;
     const float* meas = y + (int64_t)bc * g.Hi * g.Wi;
@@ -821,8 +784,7 @@ __global__ __launch_bounds__(256) void conv3d_pad_kernel(ConvGeom3 g, const floa
     DINV_DYN_LDS(float, ks);
     const int nk = g.d * g.h * g.w;
     const int z = blockIdx.z + g.z0, bc = z / g.Do, ko = z - bc * g.Do, b = bc / g.C, c = bc % g.C;
-    const float* kf = k + ((int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0)) * nk;
-    for (int i = threadIdx.x; i < nk; i += 256) ks[i] = kf[nk - 1 - i];
+    load_flipped(ks, k + plane_index(b, c, g.fb, g.fc) * nk, nk);
     __syncthreads();
     const int jo = blockIdx.x * 64 + (threadIdx.x & 63);
     const int io = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -851,8 +813,7 @@ __global__ __launch_bounds__(256) void conv3d_pad_transpose_kernel(ConvGeom3 g, 
     DINV_DYN_LDS(float, ks);
     const int nk = g.d * g.h * g.w;
     const int z = blockIdx.z + g.z0, bc = z / g.D, dd = z - bc * g.D, b = bc / g.C, c = bc % g.C;
-    const float* kf = k + ((int64_t)(g.fb > 1 ? b : 0) * g.fc + (g.fc > 1 ? c : 0)) * nk;
-    for (int i = threadIdx.x; i < nk; i += 256) ks[i] = kf[nk - 1 - i];
+    load_flipped(ks, k + plane_index(b, c, g.fb, g.fc) * nk, nk);
     __syncthreads();
     const int cc = blockIdx.x * 64 + (threadIdx.x & 63);
     const int r = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -1246,37 +1207,36 @@ extern "C" int dinv_conv2d_out_size(const dinv_conv_desc* d, int32_t* ho, int32_
     return 0;
 }
 
-extern "C" int dinv_conv2d(const dinv_conv_desc* d, const float* x, const float* filter, float* y, dinv_stream_t stream) {
+// the convolution (in = x, out = y) or its transpose (in = y, out = x): the tiled kernel, else the strided one, else the general one
+static int run_conv2d(const dinv_conv_desc* d, bool transpose, const float* in, const float* filter, float* out, dinv_stream_t stream) {
     ConvGeom g;
     if (int e = make_geom(d, &g)) return e;
     if (g.B == 0) return 0;
-    DINV_REQUIRE(x && filter && y, "null pointer");
+    DINV_REQUIRE(in && filter && out, "null pointer");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int took = 0;
-    if (int e = launch_tiled(g, false, x, filter, y, reinterpret_cast<hipStream_t>(stream), &took)) return e;
+    if (int e = launch_tiled(g, transpose, in, filter, out, s, &took)) return e;
     if (took) return 0;
-    if (int e = launch_strided(g, false, x, filter, y, reinterpret_cast<hipStream_t>(stream), &took)) return e;
+    if (int e = launch_strided(g, transpose, in, filter, out, s, &took)) return e;
     if (took) return 0;
-    hipLaunchKernelGGL(conv2d_pad_kernel, dim3((g.Wo + 63) / 64, (g.Ho + 3) / 4, g.B * g.C), dim3(256),
-                       g.h * g.w * sizeof(float), reinterpret_cast<hipStream_t>(stream), g, x, filter, y);
+    if (!transpose) {
+        hipLaunchKernelGGL(conv2d_pad_kernel, dim3((g.Wo + 63) / 64, (g.Ho + 3) / 4, g.B * g.C), dim3(256), g.h * g.w * sizeof(float), s, g,
+                           in, filter, out);
+    } else {
+        hipLaunchKernelGGL(conv2d_pad_transpose_kernel, dim3((g.W + 63) / 64, (g.H + 3) / 4, g.B * g.C), dim3(256),
+                           g.h * g.w * sizeof(float), s, g, in, filter, out);
+    }
     DINV_CHECK_LAUNCH();
     return 0;
 }
 
+extern "C" int dinv_conv2d(const dinv_conv_desc* d, const float* x, const float* filter, float* y, dinv_stream_t stream) {
+    return run_conv2d(d, false, x, filter, y, stream);
+}
+
 extern "C" int dinv_conv2d_transpose(const dinv_conv_desc* d, const float* y, const float* filter, float* x,
                                      dinv_stream_t stream) {
-    ConvGeom g;
-    if (int e = make_geom(d, &g)) return e;
-    if (g.B == 0) return 0;
-    DINV_REQUIRE(x && filter && y, "null pointer");
-    int took = 0;
-    if (int e = launch_tiled(g, true, y, filter, x, reinterpret_cast<hipStream_t>(stream), &took)) return e;
-    if (took) return 0;
-    if (int e = launch_strided(g, true, y, filter, x, reinterpret_cast<hipStream_t>(stream), &took)) return e;
-    if (took) return 0;
-    hipLaunchKernelGGL(conv2d_pad_transpose_kernel, dim3((g.W + 63) / 64, (g.H + 3) / 4, g.B * g.C), dim3(256),
-                       g.h * g.w * sizeof(float), reinterpret_cast<hipStream_t>(stream), g, y, filter, x);
-    DINV_CHECK_LAUNCH();
-    return 0;
+    return run_conv2d(d, true, y, filter, x, stream);
 }
 
 extern "C" int dinv_conv2d_filter_grad(const dinv_conv_desc* d, const float* x, const float* gy, float* dk_planes,

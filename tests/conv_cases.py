@@ -1,5 +1,5 @@
 """Shared by tests/test_conv_gpu.py (the gfx950 library) and tests/test_emu_conv.py (the same kernel sources on the host emulation):
-one table of spatial-convolution cases, each meant to reach one dispatch path of csrc/blur.hip (make_geom, launch_tiled,
+one table of spatial-convolution cases, each meant to reach one dispatch path of csrc/blur.hip (make_geom, make_tile / launch_tiled,
 launch_strided, the generic kernels, make_geom3) at one of its edges, the fp64 references, a restatement of the dispatch rules
 (expected_kernel), and the runner that calls the C entry points (dinv_conv2d, dinv_conv2d_transpose, dinv_conv2d_filter_grad and
 the three dinv_conv3d*) on guarded buffers (fft_cases.Guarded).
@@ -143,7 +143,7 @@ def rejection(d):
 
 
 def tiled_lds(h, w):
-    """launch_tiled: filter table of h + 6 rows of w4, patch of 64 + h - 1 rows of pitch 64 + w4"""
+    """make_tile: filter table of h + 6 rows of w4, patch of 64 + h - 1 rows of pitch 64 + w4"""
     w4 = (w + 3) & ~3
     return ((h + 6) * w4 + (64 + h - 1) * (64 + w4)) * 4
 
