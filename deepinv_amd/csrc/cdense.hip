@@ -11,7 +11,8 @@
 //   transposed = 0   M is [R, K], row stride ldm (in complex elements):  M[r, k]
 //   transposed = 1   M is [K, R], row stride ldm:                         M[k, r]     (B_adjoint reads _A itself: _A.conj().T)
 //   conj = 1         the conjugate of either
-// The design is that of dense.hip.  One wave owns 32 output columns r, one slice of K and up to 32 NI input rows; lane l supplies
+// The design is that of dense.hip, and the tile constants, the K-slice and workspace rules, the checks, the grid and the dispatch are
+// the same code (dense_core.hpp); the host check of the epilogue is that of common.hpp, shared with cstructured.hip.  One wave owns 32 output columns r, one slice of K and up to 32 NI input rows; lane l supplies
 // row (l & 31) and the 8 consecutive k's of half (l >> 5) of a block of 16 (64 contiguous bytes of a row of M per lane, or for
 // transposed = 1 eight loads that each cover 256 contiguous bytes per half wave).  A complex multiply-accumulate is four
 // v_mfma_f32_32x32x2_f32: re += xr mr, re += (-xi) mi, im += xr mi, im += xi mr; conjugation is the sign of mi, applied once where M
@@ -19,20 +20,15 @@
 // slice writes its partial tile to the workspace [S, I, R] and cdense_reduce_kernel adds the slices in index order: no atomics,
 // bit-reproducible.  The epilogue is applied where the finished sum is at hand: in the store of the single-slice path, in the
 // reduce kernel otherwise.
-#include "common.hpp"
+#include "dense_core.hpp"
 
 using namespace dinv;
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTile = 32;       // rows of M (output columns) per wave, and input rows per accumulator pair
 constexpr int kBlockK = 16;     // complex k's per step: 8 per half wave
 constexpr int kHalfK = 8;
-constexpr int kMaxNI = 4;       // accumulator pairs per wave: up to 128 input rows stream M once
-constexpr int kTargetWaves = 1024;  // 4 per compute unit of an MI355X
-constexpr int kMinSliceK = 64;   // the shortest slice of a batch of 32 rows or more; fewer rows allow shorter ones (split_k)
+constexpr DenseScalar kComplex{"cdense", (int)sizeof(float2), kBlockK, true};
 
 struct CDenseArgs {
     const float2* in;
@@ -184,76 +180,32 @@ __global__ __launch_bounds__(256) void cdense_reduce_kernel(const float2* __rest
     }
 }
 
-// slices of K: enough waves for the chip, each a multiple of kBlockK.  A function of the shape only.  A slice costs 2 I values of
-// workspace traffic per output column against the min_k it reads of M, so none is shorter than 2 I k's (at most kMinSliceK, at
-// least one block).  Short slices are also what keeps a small batch accurate: a matrix-core accumulator then rounds a chain of
-// only a few products, and the slices meet in double (cdense_reduce_kernel).
-void split_k(int64_t I, int64_t K, int64_t R, int64_t* S, int64_t* kchunk) {
-    const int64_t tiles = ceil_div(R, kTile) * ceil_div(I, (int64_t)kTile * kMaxNI);
-    int64_t s = kTargetWaves / tiles;
-    int64_t min_k = ceil_div(2 * I, (int64_t)kBlockK) * kBlockK;
-    if (min_k > kMinSliceK) min_k = kMinSliceK;
-    const int64_t most = ceil_div(K, min_k);
-    if (s > most) s = most;
-    if (s < 1) s = 1;
-    const int64_t c = ceil_div(ceil_div(K, s), kBlockK) * kBlockK;
-    *kchunk = c;
-    *S = ceil_div(K, c);
-}
-
-
 }  // namespace
 
-extern "C" size_t dinv_cdense_workspace_bytes(int64_t I, int64_t K, int64_t R) {
-    if (I < 1 || K < 1 || R < 1) return 0;
-    int64_t S, kchunk;
-    split_k(I, K, R, &S, &kchunk);
-    return S > 1 ? (size_t)S * I * R * sizeof(float2) : 0;
-}
+extern "C" size_t dinv_cdense_workspace_bytes(int64_t I, int64_t K, int64_t R) { return dense_workspace_bytes(kComplex, I, K, R); }
 
 extern "C" int dinv_cdense_apply(const float* in, const float* M, float* out, const float* aux, int64_t I, int64_t K, int64_t R,
                                  int64_t ldm, int32_t transposed, int32_t conj, int32_t epilogue, float eps, void* workspace,
                                  size_t workspace_bytes, dinv_stream_t stream) {
-    DINV_REQUIRE(I >= 0 && K >= 1 && R >= 1, "cdense: bad shape I = %lld, K = %lld, R = %lld", (long long)I, (long long)K, (long long)R);
-    DINV_REQUIRE(epilogue >= DINV_CDENSE_NONE && epilogue <= DINV_CDENSE_AMPLITUDE, "cdense: unknown epilogue %d", epilogue);
-    if (I == 0) return 0;
-    DINV_REQUIRE(in && M && out && in != out, "cdense: operands must be non-null and out must not alias in");
-    const bool needs_aux = epilogue == DINV_CDENSE_WEIGHT || epilogue == DINV_CDENSE_AMPLITUDE;
-    DINV_REQUIRE(!needs_aux || (aux && aux != out), "cdense: epilogue %d needs a real array of the output's shape that is not the output",
-                 epilogue);
-    DINV_REQUIRE(ldm >= (transposed ? R : K), "cdense: row stride %lld of M is below its row length %lld", (long long)ldm,
-                 (long long)(transposed ? R : K));
-    DINV_REQUIRE(I * R < ((int64_t)1 << 40) && K < ((int64_t)1 << 31) && R < ((int64_t)1 << 31), "cdense: shape too large");
-    int64_t S, kchunk;
-    split_k(I, K, R, &S, &kchunk);
-    const size_t need = S > 1 ? (size_t)S * I * R * sizeof(float2) : 0;
-    DINV_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "cdense: the workspace holds %zu bytes, %zu are needed "
-                 "(dinv_cdense_workspace_bytes)", workspace_bytes, need);
+    if (int e = check_epilogue("cdense", epilogue)) return e;
+    DensePlan p;
+    if (int e = dense_plan(kComplex, in, M, out, I, K, R, ldm, transposed, workspace, workspace_bytes, &p)) return e;
+    if (p.empty) return 0;
+    if (int e = check_aux("cdense", epilogue, aux, out, "of the output's shape")) return e;
     hipStream_t st = (hipStream_t)stream;
     CDenseArgs a{};
     a.in = (const float2*)in; a.M = (const float2*)M;
-    a.dst = S > 1 ? (float2*)workspace : nullptr;
-    a.out = out; a.aux = needs_aux ? aux : nullptr;
-    a.I = I; a.K = K; a.R = R; a.ldm = ldm; a.kchunk = kchunk;
+    a.dst = p.S > 1 ? (float2*)workspace : nullptr;
+    a.out = out; a.aux = needs_aux(epilogue) ? aux : nullptr;
+    a.I = I; a.K = K; a.R = R; a.ldm = ldm; a.kchunk = p.kchunk;
     a.transposed = transposed ? 1 : 0;
     a.conj = conj ? 1 : 0;
-    a.vec_in = aligned16(in) && K % 2 == 0;
-    a.vec_m = !transposed && aligned16(M) && ldm % 2 == 0;
+    a.vec_in = p.vec_in; a.vec_m = p.vec_m;
     a.epilogue = epilogue; a.eps = eps;
-    const int64_t per = (int64_t)kTile * kMaxNI;
-    const int ni = I > 2 * kTile ? 4 : (I > kTile ? 2 : 1);
-    const int64_t chunks = ni == 4 ? ceil_div(I, per) : 1;
-    DINV_REQUIRE(chunks < 65536 && S < 65536, "cdense: too many row chunks");
-    const dim3 grid((unsigned)ceil_div(R, kTile), (unsigned)S, (unsigned)chunks);
-    if (ni == 4) hipLaunchKernelGGL(cdense_partial_kernel<4>, grid, dim3(64), 0, st, a);
-    else if (ni == 2) hipLaunchKernelGGL(cdense_partial_kernel<2>, grid, dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(cdense_partial_kernel<1>, grid, dim3(64), 0, st, a);
-    DINV_CHECK_LAUNCH();
-    if (S > 1) {
-        const int64_t total = I * R;
-        const int64_t blocks = ceil_div(total, 256);
-        hipLaunchKernelGGL(cdense_reduce_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, st,
-                           (const float2*)workspace, out, a.aux, total, (int)S, (int)epilogue, eps);
+    DINV_DENSE_LAUNCH_PARTIAL(cdense_partial_kernel, p, st, a);
+    if (p.S > 1) {
+        hipLaunchKernelGGL(cdense_reduce_kernel, p.reduce_grid, dim3(256), 0, st, (const float2*)workspace, out, a.aux, p.total, (int)p.S,
+                           (int)epilogue, eps);
         DINV_CHECK_LAUNCH();
     }
     return 0;

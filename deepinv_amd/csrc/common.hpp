@@ -60,6 +60,22 @@ inline int fail(int code, const char* fmt, ...) {
 
 constexpr int kErrArg = 2;
 
+// ---------------------------------------------------------------- the host side of the DINV_CDENSE_* epilogues
+// (dinv_cdense_apply, dinv_cstructured_apply, dinv_ptycho_apply; `op` prefixes the message)
+inline bool needs_aux(int epilogue) { return epilogue == DINV_CDENSE_WEIGHT || epilogue == DINV_CDENSE_AMPLITUDE; }
+
+inline int check_epilogue(const char* op, int epilogue) {
+    DINV_REQUIRE(epilogue >= DINV_CDENSE_NONE && epilogue <= DINV_CDENSE_AMPLITUDE, "%s: unknown epilogue %d", op, epilogue);
+    return 0;
+}
+
+// the epilogues that read `aux` need it, and not as the output; `what` says which real array it is
+inline int check_aux(const char* op, int epilogue, const void* aux, const void* out, const char* what) {
+    DINV_REQUIRE(!needs_aux(epilogue) || (aux && aux != out), "%s: epilogue %d needs a real array %s that is not the output", op,
+                 epilogue, what);
+    return 0;
+}
+
 // ---------------------------------------------------------------- small device math
 __host__ __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __host__ __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }

@@ -25,9 +25,11 @@
 // epilogue f between the two transforms in LDS, and sums conj(p_l) times the result in registers, H W / 512 complex values a
 // thread.  One group: the workgroup stores the image.  Several: each stores a partial plane and ptycho_reduce_kernel adds them in
 // group order.  No atomics, fixed order: bit-reproducible for a given G.
-#include "fft_core.hpp"
-
-#include <cmath>
+//
+// The layer schedule, the two-float scale and the pad / trim validation are those of structured_common.hpp (with dst.hip); the host
+// check of the epilogue is that of common.hpp (with cdense.hip).  The device epilogue is this file's own: fp32 on a finished fp32
+// value, where cdense.hip evaluates in double on an exact sum.
+#include "structured_common.hpp"
 
 using namespace dinv;
 
@@ -43,11 +45,11 @@ struct CStructArgs {
     int64_t diag_planes;
     int h_in, w_in, h_out, w_out, H, W;
     int top_in, left_in, top_out, left_out;   // work (h, w) is input (h - top_in, w - left_in) and output (h - top_out, w - left_out)
-    int layers, half, adjoint, epilogue;
+    LayerSchedule sched;   // the adjoint runs the inverse transforms with the conjugated diagonals
+    int epilogue;
     int buf_elems;
     float eps;
-    float scale, scale_lo; // 1 / sqrt(H W) as an unevaluated sum of two floats, as in dst.hip: the rounding of the constant would be
-                           // a bias common to every output, which an iteration over the operator accumulates coherently
+    TwoFloat scale;        // 1 / sqrt(H W)
 };
 
 size_t buf_elems(int H, int W) {
@@ -95,11 +97,6 @@ __device__ __forceinline__ float2* plane_fft2(const dinv_fft_plan& pw, const din
     return col;
 }
 
-// z / sqrt(H W) with the constant as an unevaluated sum of two floats
-__device__ __forceinline__ float2 scaled(float2 z, float scale, float scale_lo) {
-    return make_float2(fmaf(z.x, scale, z.x * scale_lo), fmaf(z.y, scale, z.y * scale_lo));
-}
-
 // the real factor of DINV_CDENSE_WEIGHT / AMPLITUDE on the finished value v; `aux` is read for these two only
 __device__ __forceinline__ float epilogue_factor(int epilogue, float2 v, const float* aux, int64_t o, float eps) {
     float f = 1.f;
@@ -118,29 +115,24 @@ __device__ __forceinline__ void store_epilogue(int epilogue, float2 v, float* ou
     reinterpret_cast<float2*>(out)[o] = epilogue == DINV_CDENSE_NONE ? v : make_float2(v.x * f, v.y * f);
 }
 
-// diagonal applied before / after 2-D transform t of T = layers + half (-1: none).  A: [F] then (D_i, F) for i = 0 .. L - 1;
-// A_adjoint: (F^-1, conj D_{L-1-i}) for i = 0 .. L - 1, then [F^-1]
-__device__ __forceinline__ int diag_before(const CStructArgs& a, int t) { return a.adjoint ? -1 : (t >= a.half ? t - a.half : -1); }
-__device__ __forceinline__ int diag_after(const CStructArgs& a, int t) { return a.adjoint ? (t < a.layers ? a.layers - 1 - t : -1) : -1; }
-
-__device__ __forceinline__ float2 apply_diag(const CStructArgs& a, float2 v, float2 d) { return a.adjoint ? cmulc(v, d) : cmul(v, d); }
+__device__ __forceinline__ float2 apply_diag(const CStructArgs& a, float2 v, float2 d) { return a.sched.adjoint ? cmulc(v, d) : cmul(v, d); }
 
 template <bool INV>
 __device__ __forceinline__ void run_layers(const CStructArgs& a, const dinv_fft_plan& pw, const dinv_fft_plan& ph, float2* cur, float2* oth,
                                            const float2* tww, const int* permw, const float2* twh, const int* permh,
                                            const float2* dplane, int64_t dstride, int64_t plane, int tid) {
     const int H = a.H, W = a.W, LSW = fft_line_stride(W), LSH = fft_line_stride(H);
-    const int T = a.layers + a.half, total = H * W;
+    const int T = a.sched.layers + a.sched.half, total = H * W;
     for (int t = 0; t < T; ++t) {
         float2* next;
         float2* col = plane_fft2<INV>(pw, ph, cur, oth, tww, twh, permh, H, W, tid, next);
-        const int da = diag_after(a, t), db = t + 1 < T ? diag_before(a, t + 1) : -1;
+        const int da = a.sched.diag_after(t), db = t + 1 < T ? a.sched.diag_before(t + 1) : -1;
         const float2* dga = da >= 0 ? dplane + da * dstride : nullptr;
         const float2* dgb = db >= 0 ? dplane + db * dstride : nullptr;
         const bool last = t + 1 == T;
         for (int e = tid; e < total; e += kThreads) {
             const int h = e / W, w = e - h * W;
-            float2 v = scaled(col[w * LSH + h], a.scale, a.scale_lo);
+            float2 v = scaled(col[w * LSH + h], a.scale);
             if (dga) v = apply_diag(a, v, dga[e]);
             if (dgb) v = apply_diag(a, v, dgb[e]);
             if (!last) {
@@ -169,7 +161,7 @@ __global__ __launch_bounds__(kThreads) void cstructured_plane_kernel(CStructArgs
     const float2* dplane = a.diag ? a.diag + (plane % a.diag_planes) * H * W : nullptr;
     // load: pad as an index map, the first diagonal on the way, into the row layout
     {
-        const int d0 = diag_before(a, 0);
+        const int d0 = a.sched.diag_before(0);
         const float2* dg = d0 >= 0 ? dplane + d0 * dstride : nullptr;
         const float2* xp = a.x + plane * a.h_in * a.w_in;
         for (int e = tid; e < H * W; e += kThreads) {
@@ -183,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void cstructured_plane_kernel(CStructArgs
             cur[h * LSW + permw[w]] = v;
         }
     }
-    if (a.adjoint) run_layers<true>(a, pw, ph, cur, oth, tww, permw, twh, permh, dplane, dstride, plane, tid);
+    if (a.sched.adjoint) run_layers<true>(a, pw, ph, cur, oth, tww, permw, twh, permh, dplane, dstride, plane, tid);
     else run_layers<false>(a, pw, ph, cur, oth, tww, permw, twh, permh, dplane, dstride, plane, tid);
 }
 
@@ -198,7 +190,8 @@ struct PtychoArgs {
     const float* aux;      // w or y, real, [B, L, H, W]
     int H, W, L, G, groups;
     int probe_complex, epilogue, buf_elems;
-    float eps, scale, scale_lo;
+    float eps;
+    TwoFloat scale;        // 1 / sqrt(H W)
 };
 
 template <bool CONJ>
@@ -245,7 +238,7 @@ __global__ __launch_bounds__(kThreads) void ptycho_kernel(PtychoArgs a, dinv_fft
         if (OP == DINV_PTYCHO_FORWARD) {
             for (int e = tid; e < total; e += kThreads) {
                 const int h = e / W, w = e - h * W;
-                store_epilogue(a.epilogue, scaled(col[w * LSH + h], a.scale, a.scale_lo), a.out, a.aux, ol + e, a.eps);
+                store_epilogue(a.epilogue, scaled(col[w * LSH + h], a.scale), a.out, a.aux, ol + e, a.eps);
             }
             return;
         }
@@ -253,7 +246,7 @@ __global__ __launch_bounds__(kThreads) void ptycho_kernel(PtychoArgs a, dinv_fft
             // f(F p_l x, aux_l) back into the row layout, then the inverse transform of the same plane
             for (int e = tid; e < total; e += kThreads) {
                 const int h = e / W, w = e - h * W;
-                const float2 v = scaled(col[w * LSH + h], a.scale, a.scale_lo);
+                const float2 v = scaled(col[w * LSH + h], a.scale);
                 const float f = epilogue_factor(a.epilogue, v, a.aux, ol + e, a.eps);
                 next[h * LSW + s.permw[w]] = make_float2(v.x * f, v.y * f);
             }
@@ -265,7 +258,7 @@ __global__ __launch_bounds__(kThreads) void ptycho_kernel(PtychoArgs a, dinv_fft
             const int e = tid + i * kThreads;
             if (e < total) {
                 const int h = e / W, w = e - h * W;
-                acc[i] = cadd(acc[i], mul_probe<true>(a, scaled(col[w * LSH + h], a.scale, a.scale_lo), pl + e));
+                acc[i] = cadd(acc[i], mul_probe<true>(a, scaled(col[w * LSH + h], a.scale), pl + e));
             }
         }
     }
@@ -332,40 +325,31 @@ extern "C" int dinv_cstructured_apply(const float* x, float* out, const float* d
                                       float eps, const dinv_fft_plan* plan_w, const void* table_w, const dinv_fft_plan* plan_h,
                                       const void* table_h, dinv_stream_t stream) {
     DINV_REQUIRE(planes >= 0 && planes < ((int64_t)1 << 31), "cstructured: bad plane count");
-    DINV_REQUIRE(epilogue >= DINV_CDENSE_NONE && epilogue <= DINV_CDENSE_AMPLITUDE, "cstructured: unknown epilogue %d", epilogue);
+    if (int e = check_epilogue("cstructured", epilogue)) return e;
     if (planes == 0) return 0;
     DINV_REQUIRE(x && out && (const void*)x != (const void*)out, "cstructured: x and out must be non-null and distinct");
     DINV_REQUIRE(layers >= 0 && (half == 0 || half == 1) && layers + half >= 1, "cstructured: needs at least one transform "
                  "(layers = %d, half = %d)", layers, half);
     DINV_REQUIRE(layers == 0 || (diag && diag_planes >= 1), "cstructured: %d layers without diagonals", layers);
-    const bool needs_aux = epilogue == DINV_CDENSE_WEIGHT || epilogue == DINV_CDENSE_AMPLITUDE;
-    DINV_REQUIRE(!needs_aux || (aux && aux != out), "cstructured: epilogue %d needs a real array of the output's shape that is not the "
-                 "output", epilogue);
-    DINV_REQUIRE(H_in >= 1 && W_in >= 1 && H_out >= 1 && W_out >= 1, "cstructured: empty side");
-    DINV_REQUIRE(H_work == (H_in > H_out ? H_in : H_out) && W_work == (W_in > W_out ? W_in : W_out),
-                 "cstructured: the working size must be the larger of the two sides (got %d x %d for %d x %d -> %d x %d)", H_work,
-                 W_work, H_in, W_in, H_out, W_out);
-    const int h_small = H_in < H_out ? H_in : H_out, w_small = W_in < W_out ? W_in : W_out;
-    DINV_REQUIRE(top >= 0 && left >= 0 && top + h_small <= H_work && left + w_small <= W_work,
-                 "cstructured: offsets (%d, %d) put the small side outside the working one", top, left);
+    if (int e = check_aux("cstructured", epilogue, aux, out, "of the output's shape")) return e;
+    if (int e = check_pad_trim("cstructured", H_in, W_in, H_out, W_out, H_work, W_work, top, left)) return e;
     DINV_REQUIRE(dinv_cstructured_fits(H_work, W_work), "cstructured: a working plane of %d x %d needs %zu bytes of LDS for its two "
                  "buffers and tables, a workgroup has %zu (dinv_cstructured_fits)", H_work, W_work, lds_bytes(H_work, W_work), kMaxLdsBytes);
     DINV_REQUIRE(plan_w && table_w && plan_h && table_h, "cstructured: null plan / table");
     DINV_REQUIRE(plan_w->n == W_work && plan_h->n == H_work, "cstructured: the plans are for lengths %d and %d, the working plane is "
                  "%d x %d", plan_h->n, plan_w->n, H_work, W_work);
     CStructArgs a{};
-    a.x = (const float2*)x; a.out = out; a.diag = layers ? (const float2*)diag : nullptr; a.aux = needs_aux ? aux : nullptr;
+    a.x = (const float2*)x; a.out = out; a.diag = layers ? (const float2*)diag : nullptr; a.aux = needs_aux(epilogue) ? aux : nullptr;
     a.diag_planes = layers ? diag_planes : 1;
     a.h_in = H_in; a.w_in = W_in; a.h_out = H_out; a.w_out = W_out; a.H = H_work; a.W = W_work;
     a.top_in = H_in < H_work ? top : 0;
     a.left_in = W_in < W_work ? left : 0;
     a.top_out = H_out < H_work ? top : 0;
     a.left_out = W_out < W_work ? left : 0;
-    a.layers = layers; a.half = half; a.adjoint = adjoint ? 1 : 0; a.epilogue = epilogue; a.eps = eps;
+    a.sched = {layers, half, adjoint ? 1 : 0};
+    a.epilogue = epilogue; a.eps = eps;
     a.buf_elems = (int)buf_elems(H_work, W_work);
-    const double sc = 1.0 / std::sqrt((double)H_work * (double)W_work);
-    a.scale = (float)sc;
-    a.scale_lo = (float)(sc - (double)a.scale);
+    a.scale = make_two_float(1.0 / std::sqrt((double)H_work * (double)W_work));
     const size_t lds = lds_bytes(H_work, W_work);
     if (lds > kDefaultLdsBytes)
         if (int e = raise_lds_cap<cstructured_plane_kernel>(kMaxLdsBytes)) return e;
@@ -386,18 +370,16 @@ extern "C" int dinv_ptycho_apply(const float* x, float* out, const void* probe, 
                                  const dinv_fft_plan* plan_w, const void* table_w, const dinv_fft_plan* plan_h, const void* table_h,
                                  void* workspace, size_t workspace_bytes, dinv_stream_t stream) {
     DINV_REQUIRE(op >= DINV_PTYCHO_FORWARD && op <= DINV_PTYCHO_NORMAL, "ptycho: unknown operation %d", op);
-    DINV_REQUIRE(epilogue >= DINV_CDENSE_NONE && epilogue <= DINV_CDENSE_AMPLITUDE, "ptycho: unknown epilogue %d", epilogue);
-    const bool needs_aux = epilogue == DINV_CDENSE_WEIGHT || epilogue == DINV_CDENSE_AMPLITUDE;
+    if (int e = check_epilogue("ptycho", epilogue)) return e;
     DINV_REQUIRE(op != DINV_PTYCHO_ADJOINT || epilogue == DINV_CDENSE_NONE, "ptycho: the adjoint has no epilogue (got %d)", epilogue);
-    DINV_REQUIRE(op != DINV_PTYCHO_NORMAL || needs_aux, "ptycho: the normal operation applies DINV_CDENSE_WEIGHT or _AMPLITUDE between "
+    DINV_REQUIRE(op != DINV_PTYCHO_NORMAL || needs_aux(epilogue), "ptycho: the normal operation applies DINV_CDENSE_WEIGHT or _AMPLITUDE between "
                  "its transforms (got epilogue %d)", epilogue);
     DINV_REQUIRE(n_img >= 1 && H >= 1 && W >= 1, "ptycho: empty shape (n_img = %d, plane %d x %d)", n_img, H, W);
     DINV_REQUIRE(batch >= 0 && batch * n_img < ((int64_t)1 << 31), "ptycho: bad plane count (%lld x %d)", (long long)batch, n_img);
     DINV_REQUIRE(group >= 0, "ptycho: group %d (0 = automatic, > 0 = positions per workgroup, at most n_img)", group);
     if (batch == 0) return 0;
     DINV_REQUIRE(x && out && probe && (const void*)x != (const void*)out, "ptycho: x, out and probe must be non-null, x and out distinct");
-    DINV_REQUIRE(!needs_aux || (aux && aux != out), "ptycho: epilogue %d needs a real array [batch, n_img, H, W] that is not the output",
-                 epilogue);
+    if (int e = check_aux("ptycho", epilogue, aux, out, "[batch, n_img, H, W]")) return e;
     DINV_REQUIRE(dinv_cstructured_fits(H, W), "ptycho: a plane of %d x %d needs %zu bytes of LDS for its two buffers and tables, a "
                  "workgroup has %zu (dinv_cstructured_fits)", H, W, lds_bytes(H, W), kMaxLdsBytes);
     DINV_REQUIRE((int64_t)H * W <= (int64_t)kThreads * kMaxAcc, "ptycho: a plane of %d x %d exceeds the %d values a workgroup sums in "
@@ -406,13 +388,11 @@ extern "C" int dinv_ptycho_apply(const float* x, float* out, const void* probe, 
     DINV_REQUIRE(plan_w->n == W && plan_h->n == H, "ptycho: the plans are for lengths %d and %d, the plane is %d x %d", plan_h->n,
                  plan_w->n, H, W);
     PtychoArgs a{};
-    a.x = (const float2*)x; a.out = out; a.probe = probe; a.aux = needs_aux ? aux : nullptr;
+    a.x = (const float2*)x; a.out = out; a.probe = probe; a.aux = needs_aux(epilogue) ? aux : nullptr;
     a.H = H; a.W = W; a.L = n_img; a.G = 1; a.groups = n_img;
     a.probe_complex = probe_complex ? 1 : 0; a.epilogue = epilogue; a.eps = eps;
     a.buf_elems = (int)buf_elems(H, W);
-    const double sc = 1.0 / std::sqrt((double)H * (double)W);
-    a.scale = (float)sc;
-    a.scale_lo = (float)(sc - (double)a.scale);
+    a.scale = make_two_float(1.0 / std::sqrt((double)H * (double)W));
     hipStream_t st = (hipStream_t)stream;
     if (op == DINV_PTYCHO_FORWARD) return ptycho_launch<DINV_PTYCHO_FORWARD>(a, batch * n_img, plan_w, table_w, plan_h, table_h, st);
     a.G = ptycho_group(batch, n_img, H, W, group);

@@ -16,19 +16,16 @@
 // any size) are zero-filled in registers; M is never copied.
 // K is split over gridDim.y slices so that more than R / 32 waves stream M; every slice writes its partial tile to the workspace
 // [S, I, R] and dense_reduce_kernel adds the slices in index order: no atomics, bit-reproducible.  One slice writes `out` itself.
-#include "common.hpp"
+// The tile constants, the K-slice and workspace rules, the checks, the grid and the dispatch are those of dense_core.hpp, shared
+// with cdense.hip; this file holds the fp32 kernels and what they are given.
+#include "dense_core.hpp"
 
 using namespace dinv;
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTile = 32;       // rows of M (output columns) per wave, and input rows per accumulator
 constexpr int kBlockK = 32;     // k's per step: 16 per half wave
-constexpr int kMaxNI = 4;       // accumulators per wave: up to 128 input rows stream M once
-constexpr int kTargetWaves = 1024;  // 4 per compute unit of an MI355X
-constexpr int kMinSliceK = 64;
+constexpr DenseScalar kReal{"dense", (int)sizeof(float), kBlockK, false};
 
 struct DenseArgs {
     const float* in;
@@ -123,63 +120,25 @@ __global__ __launch_bounds__(256) void dense_reduce_kernel(const float* __restri
     }
 }
 
-// slices of K: enough waves for the chip, none shorter than kMinSliceK, each a multiple of kBlockK.  A function of the shape only.
-void split_k(int64_t I, int64_t K, int64_t R, int64_t* S, int64_t* kchunk) {
-    const int64_t tiles = ceil_div(R, kTile) * ceil_div(I, (int64_t)kTile * kMaxNI);
-    int64_t s = kTargetWaves / tiles;
-    const int64_t most = ceil_div(K, kMinSliceK);
-    if (s > most) s = most;
-    if (s < 1) s = 1;
-    const int64_t c = ceil_div(ceil_div(K, s), kBlockK) * kBlockK;
-    *kchunk = c;
-    *S = ceil_div(K, c);
-}
-
-
 }  // namespace
 
-extern "C" size_t dinv_dense_workspace_bytes(int64_t I, int64_t K, int64_t R) {
-    if (I < 1 || K < 1 || R < 1) return 0;
-    int64_t S, kchunk;
-    split_k(I, K, R, &S, &kchunk);
-    return S > 1 ? (size_t)S * I * R * sizeof(float) : 0;
-}
+extern "C" size_t dinv_dense_workspace_bytes(int64_t I, int64_t K, int64_t R) { return dense_workspace_bytes(kReal, I, K, R); }
 
 extern "C" int dinv_dense_apply(const float* in, const float* M, float* out, int64_t I, int64_t K, int64_t R, int64_t ldm,
                                 int32_t transposed, void* workspace, size_t workspace_bytes, dinv_stream_t stream) {
-    DINV_REQUIRE(I >= 0 && K >= 1 && R >= 1, "dense: bad shape I = %lld, K = %lld, R = %lld", (long long)I, (long long)K, (long long)R);
-    if (I == 0) return 0;
-    DINV_REQUIRE(in && M && out && in != out, "dense: operands must be non-null and out must not alias in");
-    DINV_REQUIRE(ldm >= (transposed ? R : K), "dense: row stride %lld of M is below its row length %lld", (long long)ldm,
-                 (long long)(transposed ? R : K));
-    DINV_REQUIRE(I * R < ((int64_t)1 << 40) && K < ((int64_t)1 << 31) && R < ((int64_t)1 << 31), "dense: shape too large");
-    int64_t S, kchunk;
-    split_k(I, K, R, &S, &kchunk);
-    const size_t need = S > 1 ? (size_t)S * I * R * sizeof(float) : 0;
-    DINV_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "dense: the workspace holds %zu bytes, %zu are needed "
-                 "(dinv_dense_workspace_bytes)", workspace_bytes, need);
+    DensePlan p;
+    if (int e = dense_plan(kReal, in, M, out, I, K, R, ldm, transposed, workspace, workspace_bytes, &p)) return e;
+    if (p.empty) return 0;
     hipStream_t st = (hipStream_t)stream;
     DenseArgs a{};
     a.in = in; a.M = M;
-    a.dst = S > 1 ? (float*)workspace : out;
-    a.I = I; a.K = K; a.R = R; a.ldm = ldm; a.kchunk = kchunk;
+    a.dst = p.S > 1 ? (float*)workspace : out;
+    a.I = I; a.K = K; a.R = R; a.ldm = ldm; a.kchunk = p.kchunk;
     a.transposed = transposed ? 1 : 0;
-    a.vec_in = aligned16(in) && K % 4 == 0;
-    a.vec_m = !transposed && aligned16(M) && ldm % 4 == 0;
-    const int64_t per = (int64_t)kTile * kMaxNI;
-    const int ni = I > 2 * kTile ? 4 : (I > kTile ? 2 : 1);
-    const int64_t chunks = ni == 4 ? ceil_div(I, per) : 1;
-    DINV_REQUIRE(chunks < 65536 && S < 65536, "dense: too many row chunks");
-    const dim3 grid((unsigned)ceil_div(R, kTile), (unsigned)S, (unsigned)chunks);
-    if (ni == 4) hipLaunchKernelGGL(dense_partial_kernel<4>, grid, dim3(64), 0, st, a);
-    else if (ni == 2) hipLaunchKernelGGL(dense_partial_kernel<2>, grid, dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(dense_partial_kernel<1>, grid, dim3(64), 0, st, a);
-    DINV_CHECK_LAUNCH();
-    if (S > 1) {
-        const int64_t total = I * R;
-        const int64_t blocks = ceil_div(total, 256);
-        hipLaunchKernelGGL(dense_reduce_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, st,
-                           (const float*)workspace, out, total, (int)S);
+    a.vec_in = p.vec_in; a.vec_m = p.vec_m;
+    DINV_DENSE_LAUNCH_PARTIAL(dense_partial_kernel, p, st, a);
+    if (p.S > 1) {
+        hipLaunchKernelGGL(dense_reduce_kernel, p.reduce_grid, dim3(256), 0, st, (const float*)workspace, out, p.total, (int)p.S);
         DINV_CHECK_LAUNCH();
     }
     return 0;

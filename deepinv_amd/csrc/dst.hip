@@ -21,9 +21,8 @@
 // the store).  The row pad / trim is a row-index map: only the rows present on both sides are transformed, the padded output
 // rows of a forward oversampling call are written as zeros by the same launch and the trimmed ones are never read.
 // HBM traffic: x once, the diagonals once, y once.  No atomics, fixed order: bit-reproducible.
-#include "fft_core.hpp"
-
-#include <cmath>
+// The layer schedule, the two-float scale and the pad / trim validation are those of structured_common.hpp (with cstructured.hip).
+#include "structured_common.hpp"
 
 using namespace dinv;
 
@@ -45,16 +44,10 @@ struct DstArgs {
     int w_in, w_out, n;    // n = W_work, the transform length
     int row_in0, row_out0, row_work0;   // row of transformed row t inside its plane, on each side
     int col_in0, col_out0;              // work column c is input column c - col_in0 and output column c - col_out0
-    int layers, half, adjoint;
+    LayerSchedule sched;   // the transform is its own inverse and the diagonals are real: the adjoint only reverses the order
     int lines;
-    float scale, scale_lo; // 1 / sqrt(P) as an unevaluated sum of two floats: the rounding of the constant would be a bias common to
-                           // every output, which an iteration over the operator accumulates coherently
+    TwoFloat scale;        // 1 / sqrt(P)
 };
-
-// diagonal applied before / after transform t of T = layers + half (-1: none).  A: [F] then (D_i, F) for i = 0 .. L - 1;
-// A_adjoint: (F, D_{L-1-i}) for i = 0 .. L - 1, then [F]
-__device__ __forceinline__ int diag_before(const DstArgs& a, int t) { return a.adjoint ? -1 : (t >= a.half ? t - a.half : -1); }
-__device__ __forceinline__ int diag_after(const DstArgs& a, int t) { return a.adjoint ? (t < a.layers ? a.layers - 1 - t : -1) : -1; }
 
 struct RowRef {
     int64_t in, out, diag;  // float offsets of the row's first work column on each side (in / out: may point before the row)
@@ -106,7 +99,7 @@ __global__ __launch_bounds__(kThreads) void dst_tile_kernel(DstArgs a, dinv_fft_
     const int64_t left = a.rows - g0;
     const int nrows = (int)(left < 2 * a.lines ? left : 2 * a.lines);
     const int nl = (nrows + 1) / 2;
-    const int T = a.layers + a.half;
+    const int T = a.sched.layers + a.sched.half;
 
     // a group of tpl threads (the power of two that covers a row, at most the workgroup) walks the columns of one line, so the row
     // references - two 64-bit divisions each - are worked out once per line, not per element
@@ -118,7 +111,7 @@ __global__ __launch_bounds__(kThreads) void dst_tile_kernel(DstArgs a, dinv_fft_
     float2* cur = L.buf;
     float2* oth = L.alt;
     {
-        const int d0 = diag_before(a, 0);
+        const int d0 = a.sched.diag_before(0);
         const float* dg = d0 >= 0 ? a.diag + (int64_t)d0 * a.diag_layer : nullptr;
         for (int l = lg; l < nl; l += G) {
             const RowRef ra = row_ref(a, g0 + 2 * l), rb = row_ref(a, g0 + 2 * l + 1);
@@ -138,7 +131,7 @@ __global__ __launch_bounds__(kThreads) void dst_tile_kernel(DstArgs a, dinv_fft_
     for (int t = 0; t < T; ++t) {
         float2* res = tile_fft<false>(plan, cur, oth, L.tw, nl, LS, tid, kThreads);
         float2* free_buf = res == cur ? oth : cur;
-        const int da = diag_after(a, t), db = t + 1 < T ? diag_before(a, t + 1) : -1;
+        const int da = a.sched.diag_after(t), db = t + 1 < T ? a.sched.diag_before(t + 1) : -1;
         const float* dga = da >= 0 ? a.diag + (int64_t)da * a.diag_layer : nullptr;
         const float* dgb = db >= 0 ? a.diag + (int64_t)db * a.diag_layer : nullptr;
         const bool last = t + 1 == T;
@@ -146,7 +139,7 @@ __global__ __launch_bounds__(kThreads) void dst_tile_kernel(DstArgs a, dinv_fft_
             const RowRef ra = row_ref(a, g0 + 2 * l), rb = row_ref(a, g0 + 2 * l + 1);
             for (int c = lc; c < n; c += tpl) {
                 const float2 z = res[l * LS + c + 1];
-                float va = fmaf(z.y, a.scale, z.y * a.scale_lo), vb = -fmaf(z.x, a.scale, z.x * a.scale_lo);
+                float va = scaled(z.y, a.scale), vb = -scaled(z.x, a.scale);
                 if (dga) {
                     va *= dga[ra.diag + c];
                     if (rb.live) vb *= dga[rb.diag + c];
@@ -190,9 +183,7 @@ int launch(DstArgs a, const dinv_fft_plan* plan, const void* table, hipStream_t 
     const int64_t want = ceil_div(pairs, 256);
     if (want < lines) lines = (int)(want < 1 ? 1 : want);
     a.lines = lines;
-    const double sc = 1.0 / std::sqrt((double)P);
-    a.scale = (float)sc;
-    a.scale_lo = (float)(sc - (double)a.scale);
+    a.scale = make_two_float(1.0 / std::sqrt((double)P));
     int64_t blocks = ceil_div(pairs, lines);
     if (blocks < 1) blocks = 1;      // zero rows only
     DINV_REQUIRE(blocks < ((int64_t)1 << 31), "dst: too many rows");
@@ -221,7 +212,7 @@ extern "C" int dinv_dst1(const float* x, float* out, int64_t rows, int32_t n, co
     a.rows = rows; a.diag_rows = 1;
     a.h_tr = a.h_in = a.h_out = a.h_work = 1;
     a.w_in = a.w_out = a.n = n;
-    a.half = 1;
+    a.sched.half = 1;
     return launch(a, plan, table, (hipStream_t)stream);
 }
 
@@ -235,13 +226,8 @@ extern "C" int dinv_structured_apply(const float* x, float* out, const float* di
     DINV_REQUIRE(layers >= 0 && (half == 0 || half == 1) && layers + half >= 1, "structured: needs at least one transform "
                  "(layers = %d, half = %d)", layers, half);
     DINV_REQUIRE(layers == 0 || diag, "structured: %d layers without diagonals", layers);
-    DINV_REQUIRE(H_in >= 1 && W_in >= 1 && H_out >= 1 && W_out >= 1, "structured: empty side");
-    DINV_REQUIRE(H_work == (H_in > H_out ? H_in : H_out) && W_work == (W_in > W_out ? W_in : W_out),
-                 "structured: the working size must be the larger of the two sides (got %d x %d for %d x %d -> %d x %d)", H_work,
-                 W_work, H_in, W_in, H_out, W_out);
-    const int h_tr = H_in < H_out ? H_in : H_out, w_tr = W_in < W_out ? W_in : W_out;
-    DINV_REQUIRE(top >= 0 && left >= 0 && top + h_tr <= H_work && left + w_tr <= W_work,
-                 "structured: offsets (%d, %d) put the small side outside the working one", top, left);
+    if (int e = check_pad_trim("structured", H_in, W_in, H_out, W_out, H_work, W_work, top, left)) return e;
+    const int h_tr = H_in < H_out ? H_in : H_out;
     DINV_REQUIRE((H_in == H_work || top + H_in <= H_work) && diag_rows >= 1, "structured: bad geometry");
     DstArgs a{};
     a.x = x; a.out = out; a.diag = diag;
@@ -257,6 +243,6 @@ extern "C" int dinv_structured_apply(const float* x, float* out, const float* di
     a.col_in0 = W_in < W_work ? left : 0;
     a.col_out0 = W_out < W_work ? left : 0;
     a.zero_total = planes * (int64_t)(H_out - h_tr) * W_out;
-    a.layers = layers; a.half = half; a.adjoint = adjoint ? 1 : 0;
+    a.sched = {layers, half, adjoint ? 1 : 0};
     return launch(a, plan, table, (hipStream_t)stream);
 }

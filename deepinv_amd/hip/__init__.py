@@ -138,6 +138,25 @@ def check(rc: int):
         raise RuntimeError(f"libdeepinv_amd error {rc}: {msg.decode() if msg else '?'}")
 
 
+def matrix_operand(M: torch.Tensor, dtype: torch.dtype, refusal: str):
+    """(storage tensor, row stride, transposed, conj) of a 2-D matrix of ``dtype`` used as ``M[r, k]`` by the dense kernels
+    (hip/dense.py, hip/cdense.py), read where it lies: a row-major matrix as it is, the transposed view of one through the kernels'
+    transposed form, a lazily conjugated view (``is_conj()``, complex only) of either through the conj flag, anything else through
+    one contiguous copy.  ``refusal`` is the wrapper's message for another dtype, with ``{dtype}`` for the one it got."""
+    if M.dim() != 2:
+        raise ValueError(f"expected a matrix, got shape {tuple(M.shape)}")
+    if M.dtype != dtype:
+        raise TypeError(refusal.format(dtype=M.dtype))
+    conj = int(M.is_conj())
+    phys = M.conj() if conj else M          # the same storage with the conjugate bit cleared: no copy
+    R, K = phys.shape
+    if phys.stride(1) == 1 and phys.stride(0) >= K:
+        return phys, phys.stride(0), 0, conj
+    if phys.stride(0) == 1 and phys.stride(1) >= R:
+        return phys, phys.stride(1), 1, conj
+    return M.resolve_conj().contiguous(), K, 0, 0
+
+
 def require_hip(*tensors: torch.Tensor):
     """Every operand must live on one HIP device (torch device type 'cuda' on ROCm)."""
     dev = None

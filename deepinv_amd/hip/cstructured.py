@@ -9,8 +9,8 @@ Two paths compute the same thing:
 * composed: ``hip.fft.fftn`` / ``ifftn`` per layer with the pad, the diagonals, the trim and the epilogue as torch expressions on
   the device.  Taken by every larger plane.
 
-The fused call is a ``torch.autograd.Function`` whose backward is the adjoint kernel (for ``ABS2``: the ``WEIGHT`` forward, then
-the adjoint, times 2); the composed path is differentiated by autograd through its own ops.  The diagonals and the real array of
+The fused call is a ``torch.autograd.Function`` under the autograd rule of hip/epilogue.py, with the swapped geometry and the
+flipped ``adjoint`` flag as the adjoint; the composed path is differentiated by autograd through its own ops.  The diagonals and the real array of
 an epilogue are buffers of the operator: no gradient flows to them."""
 from __future__ import annotations
 
@@ -21,7 +21,8 @@ import torch.nn.functional as F
 
 from . import FftPlan, check, declare_once, fft_plan, lib, ptr, require_hip, stream_ptr
 from . import fft as hfft
-from .cdense import ABS2, AMPLITUDE, NONE, WEIGHT, operand, real_operand
+from . import epilogue as ep
+from .epilogue import ABS2, NONE, WEIGHT, operand
 
 
 def _declare(l):
@@ -84,10 +85,7 @@ def _fused(x, diag, geom, layers, half, adjoint, epilogue, aux, eps):
     x = operand(x, "the input")
     planes = int(x.shape[0])
     out = torch.empty((planes, h_out, w_out), dtype=torch.float32 if epilogue == ABS2 else torch.complex64, device=x.device)
-    if epilogue in (WEIGHT, AMPLITUDE):
-        aux = real_operand(aux, out.shape, "the weights" if epilogue == WEIGHT else "the measurements")
-    else:
-        aux = None
+    aux = ep.aux_operand(epilogue, aux, out.shape)
     if layers:
         diag = operand(diag, "the diagonals")
         if diag.numel() != layers * dplanes * H * W:
@@ -111,26 +109,17 @@ class _CStructured(torch.autograd.Function):
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        x, diag, ctx.geom, ctx.layers, ctx.half, ctx.adjoint, ctx.epilogue, aux, _ = inputs
-        if ctx.epilogue == AMPLITUDE:
-            # the gradient of AmplitudeLoss itself: a value, not a node of the graph
-            ctx.mark_non_differentiable(output)
-            return
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(x if ctx.epilogue == ABS2 else None, diag, aux if ctx.epilogue == WEIGHT else None)
+        x, diag, ctx.geom, ctx.layers, ctx.half, ctx.adjoint, epilogue, aux, _ = inputs
+        ep.setup_context(ctx, output, x, diag, epilogue, aux)
 
     @staticmethod
     def backward(ctx, g):
-        x, diag, aux = ctx.saved_tensors
+        diag = ctx.saved_tensors[1]
         i, o, w, top, left, planes = ctx.geom
         back = (o, i, w, top, left, planes)
-        run = lambda v, geom, adjoint, ep, a: _CStructured.apply(v, diag, geom, ctx.layers, ctx.half, adjoint, ep, a, 0.0)
-        if ctx.epilogue == NONE:
-            gx = run(g, back, not ctx.adjoint, NONE, None)
-        elif ctx.epilogue == ABS2:
-            gx = 2 * run(run(x, ctx.geom, ctx.adjoint, WEIGHT, g.float()), back, not ctx.adjoint, NONE, None)
-        else:
-            gx = run(g * aux, back, not ctx.adjoint, NONE, None)
+        run = lambda v, geom, adjoint, e, a: _CStructured.apply(v, diag, geom, ctx.layers, ctx.half, adjoint, e, a, 0.0)
+        gx = ep.backward(ctx, g, run=lambda v, e, a: run(v, ctx.geom, ctx.adjoint, e, a),
+                         adjoint=lambda v: run(v, back, not ctx.adjoint, NONE, None))
         return gx, None, None, None, None, None, None, None, None
 
 

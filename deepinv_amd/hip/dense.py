@@ -8,7 +8,7 @@ import ctypes
 
 import torch
 
-from . import check, declare_once, lib, ptr, require_hip, stream_ptr
+from . import check, declare_once, lib, matrix_operand, ptr, require_hip, stream_ptr
 
 
 def _declare(l):
@@ -20,21 +20,6 @@ def _declare(l):
 
 def _l():
     return declare_once(lib(), _declare)
-
-
-def _matrix(M: torch.Tensor):
-    """(storage tensor, row stride, transposed) of a 2-D fp32 matrix used as ``M[r, k]``: a row-major matrix as it is, the
-    transposed view of one (``_A.T``) through the kernel's transposed form, anything else through a contiguous copy"""
-    if M.dim() != 2:
-        raise ValueError(f"expected a matrix, got shape {tuple(M.shape)}")
-    if M.dtype != torch.float32:
-        raise TypeError(f"the dense kernel is fp32: the matrix has dtype {M.dtype}")
-    R, K = M.shape
-    if M.stride(1) == 1 and M.stride(0) >= K:
-        return M, M.stride(0), 0
-    if M.stride(0) == 1 and M.stride(1) >= R:
-        return M, M.stride(1), 1
-    return M.contiguous(), K, 0
 
 
 def _apply(x, M):
@@ -49,7 +34,8 @@ def _apply(x, M):
     out = torch.empty((I, R), dtype=x.dtype, device=x.device)
     if I == 0:
         return out
-    store, ldm, transposed = _matrix(M)
+    # a real matrix has no conjugate
+    store, ldm, transposed, _ = matrix_operand(M, torch.float32, "the dense kernel is fp32: the matrix has dtype {dtype}")
     l = _l()
     nbytes = l.dinv_dense_workspace_bytes(I, K, R)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None

@@ -15,8 +15,8 @@ Two paths compute the same thing:
 ``group`` is the number of positions a workgroup sums in registers: 0 lets the library fill the device, a positive value forces it
 (values above ``L`` mean ``L``).  Results are bit-identical from call to call for a given group size.
 
-The fused call is a ``torch.autograd.Function``: the backward of ``NONE`` is the adjoint operation, that of ``ABS2`` is
-``2 B^H (z g)``, the normal operation with ``WEIGHT``; ``AMPLITUDE`` is a value, not a node of the graph.  The probe and the real
+The fused call is a ``torch.autograd.Function`` under the autograd rule of hip/epilogue.py, with the ``ADJOINT`` operation as the
+adjoint and the ``NORMAL`` one for ``2 B^H (z g)``, the backward of ``ABS2``.  The probe and the real
 array of an epilogue are buffers of the operator: no gradient flows to them."""
 from __future__ import annotations
 
@@ -26,7 +26,8 @@ import torch
 
 from . import FftPlan, check, declare_once, fft_plan, lib, ptr, require_hip, stream_ptr
 from . import fft as hfft
-from .cdense import ABS2, AMPLITUDE, NONE, WEIGHT, operand, real_operand
+from . import epilogue as ep
+from .epilogue import ABS2, AMPLITUDE, NONE, WEIGHT, operand
 from .cstructured import _epilogue, fits
 
 FORWARD, ADJOINT, NORMAL = 0, 1, 2      # DINV_PTYCHO_*
@@ -97,10 +98,7 @@ def _fused(x, probe, op, epilogue, aux, eps, group):
         out = torch.empty((B, L, H, W), dtype=torch.float32 if epilogue == ABS2 else torch.complex64, device=x.device)
     else:
         out = torch.empty((B, H, W), dtype=torch.complex64, device=x.device)
-    if epilogue in (WEIGHT, AMPLITUDE):
-        aux = real_operand(aux, (B, L, H, W), "the weights" if epilogue == WEIGHT else "the measurements")
-    else:
-        aux = None
+    aux = ep.aux_operand(epilogue, aux, (B, L, H, W))
     if B == 0:
         return out
     l = _l()
@@ -122,30 +120,21 @@ class _Ptycho(torch.autograd.Function):
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        x, probe, ctx.op, ctx.epilogue, aux, _, ctx.group = inputs
-        if ctx.epilogue == AMPLITUDE:
-            # the gradient of AmplitudeLoss itself: a value, not a node of the graph
-            ctx.mark_non_differentiable(output)
-            return
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(x if ctx.epilogue == ABS2 else None, probe, aux if ctx.epilogue == WEIGHT else None)
+        x, probe, ctx.op, epilogue, aux, _, ctx.group = inputs
+        ep.setup_context(ctx, output, x, probe, epilogue, aux)
 
     @staticmethod
     def backward(ctx, g):
-        x, probe, aux = ctx.saved_tensors
-        run = lambda v, op, ep, a: _Ptycho.apply(v, probe, op, ep, a, 0.0, ctx.group)
-        if ctx.op == FORWARD:
-            if ctx.epilogue == NONE:
-                gx = run(g, ADJOINT, NONE, None)
-            elif ctx.epilogue == ABS2:
-                gx = 2 * run(x, NORMAL, WEIGHT, g.float())
-            else:
-                gx = run(g * aux, ADJOINT, NONE, None)
-        elif ctx.op == ADJOINT:
-            gx = run(g, FORWARD, NONE, None)
-        else:
+        _, probe, aux = ctx.saved_tensors
+        run = lambda v, op, e=NONE, a=None: _Ptycho.apply(v, probe, op, e, a, 0.0, ctx.group)
+        if ctx.op == NORMAL:
             # B^H diag(w) B is Hermitian for real weights
             gx = run(g, NORMAL, WEIGHT, aux)
+        else:
+            # FORWARD through its epilogue, or ADJOINT, which has none
+            gx = ep.backward(ctx, g, run=lambda v, e, a: run(v, FORWARD, e, a),
+                             adjoint=lambda v: run(v, ADJOINT if ctx.op == FORWARD else FORWARD),
+                             normal=lambda v, w: run(v, NORMAL, WEIGHT, w))
         return gx, None, None, None, None, None, None
 
 

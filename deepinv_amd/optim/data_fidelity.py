@@ -108,14 +108,14 @@ class AmplitudeLoss(DataFidelity):
         self.d = AmplitudeLossDistance()
 
     def grad(self, x, y, physics, *args, epsilon: float = 1e-12, **kwargs):
-        from ..hip import cdense as hcd
+        from ..hip import epilogue as hep
         from ..physics.phase_retrieval import fused_operator
 
         B = fused_operator(physics)
         if B is not None and isinstance(y, torch.Tensor) and y.dtype == torch.float32 and tuple(y.shape) == tuple(B.measurement_shape(x)):
             if hasattr(B, "normal_epilogue"):
-                return 2 * B.normal_epilogue(x, hcd.AMPLITUDE, y, epsilon)
-            return 2 * physics.B_adjoint(B.apply_epilogue(x, hcd.AMPLITUDE, y, epsilon))
+                return 2 * B.normal_epilogue(x, hep.AMPLITUDE, y, epsilon)
+            return 2 * physics.B_adjoint(B.apply_epilogue(x, hep.AMPLITUDE, y, epsilon))
         return super().grad(x, y, physics, *args, epsilon=epsilon, **kwargs)
 
 

@@ -56,7 +56,7 @@ def spectral_methods(y: torch.Tensor, physics, x: torch.Tensor = None, n_iter: i
 
     :return: the estimate, or ``(estimate, metrics)`` when ``log``.
     """
-    from ..hip import cdense as hcd
+    from ..hip import epilogue as hep
     from ..physics.phase_retrieval import fused_operator
 
     if x is None:
@@ -75,10 +75,10 @@ def spectral_methods(y: torch.Tensor, physics, x: torch.Tensor = None, n_iter: i
         diag_T = diag_T.to(x)
     for i in range(n_iter):
         if fused and hasattr(B, "normal_epilogue"):
-            x_new = B.normal_epilogue(x, hcd.WEIGHT, diag_T)
+            x_new = B.normal_epilogue(x, hep.WEIGHT, diag_T)
         else:
             if fused:
-                x_new = B.apply_epilogue(x, hcd.WEIGHT, diag_T)
+                x_new = B.apply_epilogue(x, hep.WEIGHT, diag_T)
             else:
                 x_new = physics.B(x)
                 x_new = diag_T * x_new

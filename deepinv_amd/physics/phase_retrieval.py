@@ -15,7 +15,9 @@ from torch import Tensor
 
 from ..hip import cdense as hcd
 from ..hip import cstructured as hcs
+from ..hip import epilogue as hep
 from ..hip import ptycho as hpt
+from .compressed_sensing import _GaussianMatrix
 from .forward import LinearPhysics, Physics
 from .structured_random import _changes, compare
 
@@ -24,77 +26,29 @@ def _real_like(t, shape) -> bool:
     return isinstance(t, Tensor) and t.dtype == torch.float32 and tuple(t.shape) == tuple(shape)
 
 
-class _RandomLinear(LinearPhysics):
+class _RandomLinear(_GaussianMatrix):
     """the linear operator of :class:`RandomPhaseRetrieval`: the reference's ``CompressedSensing(dtype=torch.cfloat)`` with its
     buffers ``_A``, ``_A_dagger``, ``_A_adjoint`` and ``initial_random_state``.  ``_A_adjoint`` is the view ``_A.conj().T`` and
-    the kernel reads it in place: the device holds one copy of the matrix."""
+    the kernel reads it in place: the device holds one copy of the matrix.  The pseudo-inverse is computed in complex128."""
+
+    _dtype, _pinv_dtype = torch.cfloat, torch.complex128
+    _refusal = "RandomPhaseRetrieval runs in torch.cfloat on the complex dense kernel, got dtype {dtype}"
+    _product = staticmethod(hcd.apply)
 
     def __init__(self, m: int, img_size, channelwise: bool = False, dtype: torch.dtype = torch.cfloat, device="cpu",
                  rng: torch.Generator = None, **kwargs):
-        super().__init__(device=device, **kwargs)
-        if dtype != torch.cfloat:
-            raise NotImplementedError(f"RandomPhaseRetrieval runs in torch.cfloat on the complex dense kernel, got dtype {dtype}")
-        self.name = f"CS_m{m}"
-        self.img_size = img_size
-        self.channelwise = channelwise
-        self.dtype = dtype
-        self.rng = torch.Generator(device=device) if rng is None else rng
-        self.register_buffer("initial_random_state", self.rng.get_state())
-        n = int(np.prod(img_size[1:])) if channelwise else int(np.prod(img_size))
-        _A = torch.randn((m, n), device=device, dtype=dtype, generator=self.rng) / np.sqrt(m)
-        # once, on the host in complex128: no device solver library is needed
-        _A_dagger = torch.linalg.pinv(_A.detach().cpu().to(torch.complex128)).to(dtype).to(device)
-        self.register_buffer("_A", _A)
-        self.register_buffer("_A_dagger", _A_dagger)
-        self.register_buffer("_A_adjoint", self._A.conj().T)
-        self.to(device=device)
-
-    def _apply(self, fn, *args, **kwargs):
-        # a move of the module handles every buffer on its own: tie _A_adjoint to _A again, so that it stays a view as in the
-        # reference and the device holds one copy of the matrix
-        super()._apply(fn, *args, **kwargs)
-        if "_A" in self._buffers and "_A_adjoint" in self._buffers:
-            self._buffers["_A_adjoint"] = self._buffers["_A"].conj().T
-        return self
-
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        # the state of a generator of another device type has another size: take it as it is instead of failing on the shape
-        key = prefix + "initial_random_state"
-        if key in state_dict and state_dict[key].shape != self.initial_random_state.shape:
-            self.initial_random_state = state_dict[key].clone().to(self.initial_random_state.device)
-        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
-        if "_A" in self._buffers:
-            self._buffers["_A_adjoint"] = self._buffers["_A"].conj().T
+        super().__init__(m, img_size, channelwise, dtype, device, rng, **kwargs)
 
     def measurement_shape(self, x):
         N, C = x.shape[:2]
         return (N, C, self._A.shape[0]) if self.channelwise else (N, self._A.shape[0])
 
     def apply_epilogue(self, x: Tensor, epilogue: int, aux=None, eps: float = 1e-12) -> Tensor:
-        """``B x`` through an epilogue of hip/cdense.py, in the shape of the measurements"""
-        N, C = x.shape[:2]
-        x = x.reshape(N * C, -1) if self.channelwise else x.reshape(N, -1)
+        """``B x`` through an epilogue of hip/epilogue.py, in the shape of the measurements"""
+        x, shaped = self._rows(x)
         if aux is not None:
             aux = aux.reshape(x.shape[0], -1)
-        y = hcd.apply(x, self._A, epilogue, aux, eps)
-        return y.view(N, C, -1) if self.channelwise else y
-
-    def A(self, x: Tensor, **kwargs) -> Tensor:
-        return self.apply_epilogue(x, hcd.NONE)
-
-    def _back(self, y, M):
-        y = y.type(self.dtype)
-        N = y.shape[0]
-        C, H, W = self.img_size[0], self.img_size[1], self.img_size[2]
-        if self.channelwise:
-            y = y.reshape(N * C, -1)
-        return hcd.apply(y, M).reshape(N, C, H, W)
-
-    def A_adjoint(self, y: Tensor, **kwargs) -> Tensor:
-        return self._back(y, self._A_adjoint)
-
-    def A_dagger(self, y: Tensor, **kwargs) -> Tensor:
-        return self._back(y, self._A_dagger)
+        return shaped(hcd.apply(x, self._A, epilogue, aux, eps))
 
 
 def generate_diagonal(shape: tuple, mode: str = "uniform_phase", dtype=torch.cfloat, device="cpu"):
@@ -148,7 +102,7 @@ class _StructuredLinear(LinearPhysics):
     def measurement_shape(self, x):
         return (*x.shape[:-2], int(self.output_size[1]), int(self.output_size[2]))
 
-    def _run(self, x, adjoint, epilogue=hcd.NONE, aux=None, eps=1e-12):
+    def _run(self, x, adjoint, epilogue=hep.NONE, aux=None, eps=1e-12):
         L = math.floor(self.n_layers)
         half = self.n_layers - L == 0.5
         geom = self._geometry(adjoint)
@@ -245,10 +199,10 @@ class PtychographyLinearOperator(LinearPhysics):
         return hpt.apply(self._image(x), self.probe, hpt.NORMAL, epilogue, aux, eps, group).unsqueeze(1)
 
     def A(self, x: Tensor, **kwargs) -> Tensor:
-        return self.apply_epilogue(x, hcd.NONE)
+        return self.apply_epilogue(x, hep.NONE)
 
     def A_adjoint(self, y: Tensor, group: int = 0, **kwargs) -> Tensor:
-        return hpt.apply(y.type(torch.cfloat), self.probe, hpt.ADJOINT, hcd.NONE, None, 0.0, group).unsqueeze(1)
+        return hpt.apply(y.type(torch.cfloat), self.probe, hpt.ADJOINT, hep.NONE, None, 0.0, group).unsqueeze(1)
 
     def shift(self, x, x_shift, y_shift, pad_zeros=True):
         """``x`` rolled by (``x_shift``, ``y_shift``) along the last two axes, with zeros where it wrapped (phase_retrieval.py:397-418)"""
@@ -294,7 +248,7 @@ class PhaseRetrieval(Physics):
     def A(self, x: Tensor, **kwargs) -> Tensor:
         B = fused_operator(self)
         if B is not None:
-            return B.apply_epilogue(x, hcd.ABS2)
+            return B.apply_epilogue(x, hep.ABS2)
         return self.B(x, **kwargs).abs().square()
 
     def A_dagger(self, y: Tensor, **kwargs) -> Tensor:
@@ -321,8 +275,8 @@ class PhaseRetrieval(Physics):
         B = fused_operator(self)
         if B is not None and _real_like(v, B.measurement_shape(x)):
             if hasattr(B, "normal_epilogue"):
-                return 2 * B.normal_epilogue(x, hcd.WEIGHT, v)
-            return 2 * self.B_adjoint(B.apply_epilogue(x, hcd.WEIGHT, v))
+                return 2 * B.normal_epilogue(x, hep.WEIGHT, v)
+            return 2 * self.B_adjoint(B.apply_epilogue(x, hep.WEIGHT, v))
         return 2 * self.B_adjoint(self.B(x) * v)
 
     def release_memory(self):

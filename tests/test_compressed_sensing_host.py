@@ -109,3 +109,19 @@ def test_custom_transforms_are_called_in_the_reference_order():
     # centre: Finv(1) = 11, D1: 33; Finv: 43, D0: 86; the half layer Finv: 96.  padded border: Finv(0) = 10, 30; 40, 80; 90
     assert [k for k, _ in log] == ["Finv"] * 3 and tuple(x.shape) == (1, 1, 4, 6)
     assert float(x[0, 0, 1, 1]) == 96.0 and float(x[0, 0, 0, 0]) == 90.0
+
+
+def test_adjoint_stays_a_view_after_load_state_dict():
+    from deepinv_amd.physics.phase_retrieval import _RandomLinear
+
+    for cls, conj in ((dinv.physics.CompressedSensing, False), (_RandomLinear, True)):
+        # a copying load writes into the view; an assigning load hands every buffer a storage of its own, and only the re-tie
+        # after the load makes _A_adjoint a view of the new _A again
+        for assign in (False, True):
+            src = cls(m=10, img_size=(2, 3, 3), rng=torch.Generator().manual_seed(3))
+            dst = cls(m=10, img_size=(2, 3, 3))
+            # as a checkpoint read from disk arrives: every tensor with a storage of its own
+            dst.load_state_dict({k: v.clone() for k, v in src.state_dict().items()}, assign=assign)
+            assert torch.equal(dst._A, src._A) and torch.equal(dst._A_adjoint, src._A.conj().T)
+            assert dst._A_adjoint.data_ptr() == dst._A.data_ptr() and dst._A_adjoint.is_conj() == conj, (cls.__name__, assign)
+            assert list(dst.state_dict()) == list(src.state_dict())

@@ -118,3 +118,12 @@ def test_real_operators_still_refuse_complex():
         dinv.physics.structured_random.generate_diagonal((1, 4, 4), mode="uniform_phase")
     with pytest.raises(NotImplementedError, match="phase retrieval"):
         dinv.physics.StructuredRandom((1, 4, 4), (1, 4, 4), diagonals=[torch.ones(1, 4, 4, dtype=torch.cfloat)])
+
+
+def test_random_linear_checks_the_generator_device_like_compressed_sensing():
+    kw = dict(m=10, img_size=(1, 3, 3), device="meta", rng=torch.Generator("cpu"))
+    with pytest.raises(ValueError, match="random generator") as cs:
+        dinv.physics.CompressedSensing(**kw)
+    with pytest.raises(ValueError, match="random generator") as rl:
+        PR._RandomLinear(**kw)
+    assert str(rl.value) == str(cs.value)
