@@ -121,7 +121,9 @@ __device__ __forceinline__ double poisson_log_pmf(double k, double lam) {
 // one Poisson(lam) variate for a finite lam > 0 as a double holding an integer
 __device__ __forceinline__ double poisson_draw(float lam, uint64_t seed, uint64_t ctr) {
     if (lam < POISSON_PTRS_FROM) {
-        const float limit = expf(-lam);
+        // exp(-lambda) in fp64, rounded once: the same float on every platform, so that the count is a function of (seed, counter, lambda)
+        // alone.  expf is only within its error bound of that float, and a product that lands in between changes the count.
+        const float limit = (float)exp(-(double)lam);
         float prod = 1.0f;
         int k = 0;
         for (int round = 0; round < POISSON_MAX_ROUNDS; ++round) {
