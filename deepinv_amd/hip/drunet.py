@@ -336,6 +336,27 @@ def conv_packs(w: torch.Tensor, bias: torch.Tensor | None = None, precision: str
                      bias=pack_bias(bias, cout_p) if bias is not None else None)
 
 
+class StridePacks(NamedTuple):
+    """the packs of ONE 2x2 stride-2 layer, strided or transposed, one field per kernel that may run it (None: that kernel does not
+    take the layer); `launch_down` / `launch_up` run the layer"""
+    direct: torch.Tensor                    # direct fp32 kernel: pack_down_weight / pack_up_weight
+    split: torch.Tensor | None = None       # two-part bf16 split: pack_down_bf16s_weight / pack_up_bf16s_weight
+    x3: torch.Tensor | None = None          # three-part bf16 split, six products (fp32-equivalent): pack_down_bf16x3_weight
+
+
+def stride_packs(w: torch.Tensor, up: bool = False, precision: str | None = None) -> StridePacks:
+    """StridePacks of a Conv2d [Cout,Cin,2,2] or (`up`) ConvTranspose2d [Cin,Cout,2,2] weight: the direct pack; with `precision`, also
+    the pack of that setting's kernel where the layer has its shape ("bf16split": split; "fp32": x3 - the fp32-MFMA kernel is bound
+    by that pipe -, strided layers only)"""
+    cin, cout = w.shape[:2] if up else (w.shape[1], w.shape[0])
+    ok = cout % 64 == 0 and cin % 16 == 0
+    if up:
+        return StridePacks(pack_up_weight(w), split=pack_up_bf16s_weight(w) if ok and precision == "bf16split" else None)
+    return StridePacks(pack_down_weight(w),
+                       split=pack_down_bf16s_weight(w) if ok and precision == "bf16split" else None,
+                       x3=pack_down_bf16x3_weight(w) if ok and precision == "fp32" else None)
+
+
 # Packed weights of the training / 3-D paths are cached per source tensor: an unfolded network calls the denoiser
 # `max_iter` times per training step with the same weights and every layer needs a pack (a dozen small torch ops) per
 # call otherwise - more host time than the kernels take.  One entry per (kind, storage address, shape, sub): the entry
@@ -598,6 +619,25 @@ def up2x2_bf16s(gi, go, x, x2, wsplit, cin, cout, y):
 def up2x2(gi, go, x, x2, w, cin, cout, y):
     check(_l().dinv_conv_up2x2(ctypes.byref(gi), ctypes.byref(go), ptr(x), ptr(x2), ptr(w), cin, cout, ptr(y),
                                stream_ptr(y.device)))
+
+
+def launch_down(gi, go, x, pk: StridePacks, cin, cout, y):
+    """y = the 2x2 stride-2 convolution of x, on the kernel whose pack `pk` holds (the arithmetic of the ResBlock convolutions of the
+    setting the packs were built for)"""
+    if pk.split is not None:
+        down2x2_bf16s(gi, go, x, pk.split, cin, cout, y)
+    elif pk.x3 is not None:
+        down2x2_bf16x3(gi, go, x, pk.x3, cin, cout, y)
+    else:
+        down2x2(gi, go, x, pk.direct, cin, cout, y)
+
+
+def launch_up(gi, go, x, x2, pk: StridePacks, cin, cout, y):
+    """y = the 2x2 stride-2 transposed convolution of x (+ x2), on the kernel whose pack `pk` holds"""
+    if pk.split is not None:
+        up2x2_bf16s(gi, go, x, x2, pk.split, cin, cout, y)
+    else:
+        up2x2(gi, go, x, x2, pk.direct, cin, cout, y)
 
 
 def conv_wgrad(gs, gl, s, m, l, n, taps, dw=None, accumulate=False):

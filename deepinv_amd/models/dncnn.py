@@ -100,11 +100,7 @@ class DnCNN(Denoiser):
             return self._engine
         e = {"ver": ver, "device": device, "ws": {}}
         e["head"] = _direct_packs(self.in_conv, device)
-        e["body"] = []
-        for m in self.conv_list:
-            w = m.weight.to(device)
-            wino = K.pack_winograd4_weight(w) if self.nf % 64 == 0 else None
-            e["body"].append((_direct_packs(m, device), wino))
+        e["body"] = [_direct_packs(m, device, wino4=self.nf % 64 == 0) for m in self.conv_list]
         e["tail"] = _tail_pack(self.out_conv, device)
         self._engine = e
         return e
@@ -130,9 +126,9 @@ class DnCNN(Denoiser):
         _layer(g, e["head"], ws["in"], ws["a"], self.nf, relu=True)
         cur, nxt = ws["a"], ws["b"]
         wino_ok = Hh % 4 == 0 and W % 4 == 0
-        for pk, wino in e["body"]:
-            if wino is not None and wino_ok:
-                _winograd(g, pk, wino, cur, nxt, self.nf)
+        for pk in e["body"]:
+            if pk.wino4 is not None and wino_ok:
+                _winograd(g, pk, cur, nxt, self.nf)
             else:
                 _layer(g, pk, cur, nxt, self.nf, relu=True)
             cur, nxt = nxt, cur
@@ -142,10 +138,12 @@ class DnCNN(Denoiser):
         return y
 
 
-# ---- layer helpers: a "pack" is a K.ConvPacks with the direct packs (64- / 32-wide cout tiles) and the zero-padded fp32 bias
-# (None for bias=False)
-def _direct_packs(m, device):
-    return K.conv_packs(m.weight.to(device), m.bias.to(device) if m.bias is not None else None)
+# ---- layer helpers: a "pack" is a K.ConvPacks with the direct packs (64- / 32-wide cout tiles), the zero-padded fp32 bias
+# (None for bias=False) and, for the body layers the F(4x4) kernel takes, its pack - no other: DnCNN launches no other kernel
+def _direct_packs(m, device, wino4=False):
+    w = m.weight.to(device)
+    pk = K.conv_packs(w, m.bias.to(device) if m.bias is not None else None)
+    return pk._replace(wino4=K.pack_winograd4_weight(w)) if wino4 else pk
 
 
 def _tail_pack(m, device):
@@ -169,12 +167,12 @@ def _layer(g, pk, x, y, cout, relu=False, res1=None):
         K.conv3x3(g, x, pk.pick(g), pk.cin_p, pk.cout_p, y, cout_valid=cout, res1=res1, relu=relu)
 
 
-def _winograd(g, pk, wino, x, y, nf):
+def _winograd(g, pk, x, y, nf):
     wsp = K.winograd4_workspace(x.device)
     if pk.bias is not None:
-        K.conv3x3_winograd4_bias(g, x, wino, pk.bias, nf, nf, y, relu=True, workspace=wsp)
+        K.conv3x3_winograd4_bias(g, x, pk.wino4, pk.bias, nf, nf, y, relu=True, workspace=wsp)
     else:
-        K.conv3x3_winograd4(g, x, wino, nf, nf, y, relu=True, workspace=wsp)
+        K.conv3x3_winograd4(g, x, pk.wino4, nf, nf, y, relu=True, workspace=wsp)
 
 
 def _tail(g, tp, x, res, y, cout):

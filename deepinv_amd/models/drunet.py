@@ -13,6 +13,7 @@ where it serves as an independent GPU reference).
 """
 from __future__ import annotations
 
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -101,10 +102,30 @@ _CUS: dict = {}
 
 
 def _compute_units(device) -> int:
+    if device.type != "cuda":       # (the launch recorder of tests/test_unet_launches_host.py: MI355X)
+        return 256
     idx = device.index if device.index is not None else torch.cuda.current_device()
     if idx not in _CUS:
-        _CUS[idx] = int(torch.cuda.get_device_properties(idx).multi_processor_count) if device.type == "cuda" else 256
+        _CUS[idx] = int(torch.cuda.get_device_properties(idx).multi_processor_count)
     return _CUS[idx]
+
+
+class Stage(NamedTuple):
+    """one level of the encoder or of the decoder"""
+    blocks: list                # (conv1, conv2) K.ConvPacks per ResBlock
+    stride: K.StridePacks       # the 2x2 stride-2 layer that leaves (encoder) or enters (decoder) the level
+
+
+class Engine(NamedTuple):
+    """what `DRUNet._prepare` keeps per model: the weight packs of every layer and the activation buffers"""
+    key: tuple                  # (what the packs were built from, device)
+    head: K.ConvPacks
+    tail: K.ConvPacks
+    tail_valu: torch.Tensor | None      # pack_tail_weight, where the vector-ALU kernel takes the tail
+    downs: list                 # Stage of level 0, 1, 2
+    body: list                  # blocks of level 3
+    ups: list                   # Stage of level 2, 1, 0
+    ws: dict                    # (B, H, W, lane) -> activation buffers (`_workspace`)
 
 
 class DRUNet(Denoiser):
@@ -214,59 +235,49 @@ class DRUNet(Denoiser):
         return run_four_windows(run, xin, field=64)
 
     # ------------------------------------------------------------------ MFMA inference engine
-    def _prepare(self, device):
-        ver = (K.weights_version(self), self._precision(), K.FP32_WINOGRAD4_BF16X3)     # the packs depend on the precision
-        if self._engine is not None and self._engine["ver"] == ver and self._engine["device"] == device:
+    def _prepare(self, device) -> Engine:
+        precision = self._precision()
+        key = ((K.weights_version(self), precision, K.FP32_WINOGRAD4_BF16X3), device)     # the packs depend on the precision
+        if self._engine is not None and self._engine.key == key:
             return self._engine
-        e = {"ver": ver, "device": device, "ws": {}, "split": self._precision() == "bf16split"}
-        split = e["split"]
 
         def c3(m):
             """packs of one 3x3 conv: direct fp32 (64- and 32-wide cout tiles; ConvPacks.pick chooses per launch geometry) and, per
             precision, the bf16-split packs or the fp32 Winograd packs"""
-            return K.conv_packs(m.weight.to(device), precision=self._precision())
+            return K.conv_packs(m.weight.to(device), precision=precision)
 
-        e["head"] = c3(self.m_head)
-        e["tail"] = c3(self.m_tail)
+        def stage(blocks, stride, up=False):
+            return Stage([(c3(b.res[0]), c3(b.res[2])) for b in blocks], K.stride_packs(stride.weight.to(device), up, precision))
+
         wt = self.m_tail.weight
-        e["tail_valu"] = K.pack_tail_weight(wt.to(device)) if (wt.shape[0] <= 4 and wt.shape[1] % 8 == 0) else None
-        for name in ("m_down1", "m_down2", "m_down3"):
-            seq = getattr(self, name)
-            e[name] = [(c3(b.res[0]), c3(b.res[2])) for b in list(seq)[:-1]]
-            wd = seq[-1].weight.to(device)
-            e[name + "_s"] = K.pack_down_weight(wd)
-            okd = wd.shape[0] % 64 == 0 and wd.shape[1] % 16 == 0
-            e[name + "_sb"] = K.pack_down_bf16s_weight(wd) if (split and okd) else None
-            # fp32 setting: three-part bf16 split, six products (fp32-equivalent; the fp32-MFMA kernel is bound by that pipe)
-            e[name + "_s3"] = K.pack_down_bf16x3_weight(wd) if (not split and okd) else None
         body = [self.m_body] if isinstance(self.m_body, ResBlock) else list(self.m_body)
-        e["m_body"] = [(c3(b.res[0]), c3(b.res[2])) for b in body]
-        for name in ("m_up3", "m_up2", "m_up1"):
-            seq = getattr(self, name)
-            wu = seq[0].weight.to(device)
-            e[name + "_s"] = K.pack_up_weight(wu)
-            e[name + "_sb"] = K.pack_up_bf16s_weight(wu) if (split and wu.shape[0] % 16 == 0 and wu.shape[1] % 64 == 0) else None
-            e[name] = [(c3(b.res[0]), c3(b.res[2])) for b in list(seq)[1:]]
-        self._engine = e
-        return e
+        self._engine = Engine(
+            key, head=c3(self.m_head), tail=c3(self.m_tail),
+            tail_valu=K.pack_tail_weight(wt.to(device)) if (wt.shape[0] <= 4 and wt.shape[1] % 8 == 0) else None,
+            downs=[stage(list(seq)[:-1], seq[-1]) for seq in (self.m_down1, self.m_down2, self.m_down3)],
+            body=[(c3(b.res[0]), c3(b.res[2])) for b in body],
+            ups=[stage(list(seq)[1:], seq[0], up=True) for seq in (self.m_up3, self.m_up2, self.m_up1)], ws={})
+        return self._engine
 
     def _workspace(self, e, B, H, W, device, lane=0):
         key = (B, H, W, lane)
-        ws = e["ws"].get(key)
+        ws = e.ws.get(key)
         if ws is None:
-            if any(k[1:3] != (H, W) or k[3] == lane for k in e["ws"]):
-                e["ws"].clear()  # one image geometry at a time keeps the footprint bounded (its batch lanes live side by side)
+            if any(k[1:3] != (H, W) or k[3] == lane for k in e.ws):
+                e.ws.clear()  # one image geometry at a time keeps the footprint bounded (its batch lanes live side by side)
             nc = self.nc
             g = [K.geom(B, H >> i, W >> i) for i in range(4)]
-            ws = {"g": g, "in": K.alloc(g[0], e["head"].cin_p, device), "out": K.alloc(g[0], self.out_channels, device)}
+            ws = {"g": g, "in": K.alloc(g[0], e.head.cin_p, device), "out": K.alloc(g[0], self.out_channels, device)}
             for i in range(4):
                 # skip tensor x_{i+1}, two ping-pong buffers and the ResBlock temporary
                 for nm in ("skip", "a", "b", "t"):
                     ws[f"{nm}{i}"] = K.alloc(g[i], nc[i], device)
-            e["ws"][key] = ws
+            e.ws[key] = ws
         return ws
 
-    def _conv_fp32(self, g, pk, x, y, relu=False, res1=None):
+    # ---- `tail_split` is the launch policy of ONE call (`_hip_forward_lane` takes it, `_run_lanes` passes False): an argument all
+    # the way down to the one decision it makes, the workspace of an F(4x4) launch below - never state of the model
+    def _conv_fp32(self, g, pk, x, y, relu=False, res1=None, tail_split=True):
         """one ResBlock convolution in fp32 arithmetic: Winograd F(4x4,3x3) kernel (csrc/drunet_wino4.hip) where the image
         sides are multiples of 4 and the launch has enough 64-cout x 32-tile workgroup tiles to occupy the chip, else the
         F(2x2,3x3) kernel, else the direct MFMA kernel"""
@@ -278,7 +289,7 @@ class DRUNet(Denoiser):
             # inside a batch lane the last, incomplete round of tiles is left to the other lane (see batch_lanes) - unless the
             # WHOLE launch is less than one round (fewer tiles than compute units: the deep levels of a small lane), where cutting
             # the tiles along the input channels is what fills the chip
-            wsp = K.winograd4_workspace(x.device) if (self._tail_split or tiles < _compute_units(x.device)) else None
+            wsp = K.winograd4_workspace(x.device) if (tail_split or tiles < _compute_units(x.device)) else None
             if pk.wino4x3 is not None:       # (K.FP32_WINOGRAD4_BF16X3 when the packs were built)
                 K.conv3x3_winograd4_bf16x3(g, x, pk.wino4x3, ci, co, y, res1=res1, relu=relu, workspace=wsp)
             else:
@@ -288,7 +299,7 @@ class DRUNet(Denoiser):
         else:
             K.conv3x3(g, x, pk.pick(g), ci, co, y, relu=relu, res1=res1)
 
-    def _res_block(self, g, pk1, pk2, x, t, y):
+    def _res_block(self, g, pk1, pk2, x, t, y, tail_split=True):
         """y = x + conv2(relu(conv1(x))) (drunet.py:403-434); `t` is scratch.  bf16-split precision: Winograd F(2,3) along
         rows on the bf16 matrix cores (csrc/drunet_wsplit.hip: 1.5x fewer matrix instructions, measured 12-25 % faster per
         level at 4 and 32 slices) wherever the image width is even; else the direct kernel, whose conv1 writes its ReLU output
@@ -300,18 +311,17 @@ class DRUNet(Denoiser):
             K.conv3x3_split(g, x, pk1.split2d, pk1.cin_p, pk1.cout_p, t, relu=True, y_presplit=True)
             K.conv3x3_split(g, t, pk2.split2d, pk2.cin_p, pk2.cout_p, y, res1=x, x_presplit=True)
         else:
-            self._conv_fp32(g, pk1, x, t, relu=True)
-            self._conv_fp32(g, pk2, t, y, res1=x)
+            self._conv_fp32(g, pk1, x, t, relu=True, tail_split=tail_split)
+            self._conv_fp32(g, pk2, t, y, res1=x, tail_split=tail_split)
 
-    def _res_chain(self, g, blocks, c, x, a, b, t):
-        """run ResBlocks: returns the buffer holding the result (never `x` itself is overwritten)"""
-        cur = x
-        bufs = [a, b]
+    def _res_chain(self, g, blocks, x, t, dst, tail_split):
+        """run ResBlocks on x with the scratch buffer t; returns the buffer that holds the result.  Block i reads the result of
+        block i - 1 and writes dst[i % 2], so a block never writes what it reads, and x is overwritten only where the caller
+        names it as dst[1] (block 1 reads dst[0]: x is dead by then)"""
         for i, (pk1, pk2) in enumerate(blocks):
-            dst = bufs[i % 2]
-            self._res_block(g, pk1, pk2, cur, t, dst)
-            cur = dst
-        return cur
+            self._res_block(g, pk1, pk2, x, t, dst[i % 2], tail_split)
+            x = dst[i % 2]
+        return x
 
     # ---- batch lanes: the batch cut into `batch_lanes` contiguous parts, each run through the whole network on its own HIP stream.
     # The units of a batch are independent through the network, and every convolution launch ends in an incomplete round of
@@ -327,7 +337,6 @@ class DRUNet(Denoiser):
     # unit's result then does not depend on the batch it is computed in at all (no summation order depends on the tile round).
     batch_lanes = "auto"
     LANES_MIN_PIXELS = 4 * 128 * 128
-    _tail_split = True
 
     def _lanes(self, x):
         B = x.shape[0]
@@ -352,12 +361,8 @@ class DRUNet(Denoiser):
             if isinstance(sg, torch.Tensor) and sg.numel() > 1:      # one value per sample, or a map: this lane's units
                 sg = sg.reshape(B, *sg.shape[1:])[b0:b1] if sg.shape[0] == B else sg
             s.wait_stream(cur)
-            with torch.cuda.stream(s):
-                self._tail_split = False        # (see batch_lanes: the other lane fills the last round)
-                try:
-                    self._hip_forward_lane(x[b0:b1], sg, lane=i, out=y[b0:b1])
-                finally:
-                    self._tail_split = True
+            with torch.cuda.stream(s):      # (tail_split: see batch_lanes - the other lane fills the last round)
+                self._hip_forward_lane(x[b0:b1], sg, lane=i, out=y[b0:b1], tail_split=False)
         for s in streams:
             cur.wait_stream(s)
         return y
@@ -411,8 +416,8 @@ class DRUNet(Denoiser):
                 return self._run_lanes(x, sigma_map, streams)
         return self._hip_forward_lane(x, sigma_map)
 
-    def _hip_forward_lane(self, x, sigma_map, lane=0, out=None):
-        """forward_unet (drunet.py:200-210) as 64 conv launches + pack/unpack."""
+    def _hip_forward_lane(self, x, sigma_map, lane=0, out=None, tail_split=True):
+        """forward_unet (drunet.py:200-210) as 64 conv launches + pack/unpack; `tail_split` = False is how a batch lane runs"""
         dev = x.device
         e = self._prepare(dev)
         B, _, H, W = x.shape
@@ -421,42 +426,21 @@ class DRUNet(Denoiser):
         nc = self.nc
         x = x.contiguous().float()
         K.pack_input(g[0], x, sigma_map, ws["in"])
-        hd = e["head"]
+        hd = e.head
         K.conv3x3(g[0], ws["in"], hd.pick(g[0]), hd.cin_p, hd.cout_p, ws["skip0"], cin_valid=self.in_channels + 1)  # x1
-        cur = ws["skip0"]
-        downs = ("m_down1", "m_down2", "m_down3")
-        for i, name in enumerate(downs):
-            r = self._res_chain(g[i], e[name], nc[i], cur, ws[f"a{i}"], ws[f"b{i}"], ws[f"t{i}"])
-            if e[name + "_sb"] is not None:   # same arithmetic as the ResBlock convs
-                K.down2x2_bf16s(g[i], g[i + 1], r, e[name + "_sb"], nc[i], nc[i + 1], ws[f"skip{i + 1}"])   # x2, x3, x4
-            elif e[name + "_s3"] is not None:
-                K.down2x2_bf16x3(g[i], g[i + 1], r, e[name + "_s3"], nc[i], nc[i + 1], ws[f"skip{i + 1}"])
-            else:
-                K.down2x2(g[i], g[i + 1], r, e[name + "_s"], nc[i], nc[i + 1], ws[f"skip{i + 1}"])
-            cur = ws[f"skip{i + 1}"]
-        r = self._res_chain(g[3], e["m_body"], nc[3], cur, ws["a3"], ws["b3"], ws["t3"])
-        skip_add = ws["skip3"]  # x + x4 is fused into the up-conv's operand load
-        for i, name in zip((2, 1, 0), ("m_up3", "m_up2", "m_up1")):
-            if e[name + "_sb"] is not None:
-                K.up2x2_bf16s(g[i + 1], g[i], r, skip_add, e[name + "_sb"], nc[i + 1], nc[i], ws[f"t{i}"])
-            else:
-                K.up2x2(g[i + 1], g[i], r, skip_add, e[name + "_s"], nc[i + 1], nc[i], ws[f"t{i}"])
-            # t{i} holds the up-conv output; run the ResBlocks with a/b ping-pong and a fresh temporary
-            r = self._res_chain_from_t(g[i], e[name], ws[f"t{i}"], ws[f"a{i}"], ws[f"b{i}"])
-            skip_add = ws[f"skip{i}"]
-        if e["tail_valu"] is not None:   # m_tail(x + x1)
-            K.conv3x3_tail(g[0], r, e["tail_valu"], nc[0], self.out_channels, ws["out"], x2=ws["skip0"])
+        for i, st in enumerate(e.downs):    # the skip tensor x_{i+1} survives: the blocks write a and b only
+            r = self._res_chain(g[i], st.blocks, ws[f"skip{i}"], ws[f"t{i}"], (ws[f"a{i}"], ws[f"b{i}"]), tail_split)
+            K.launch_down(g[i], g[i + 1], r, st.stride, nc[i], nc[i + 1], ws[f"skip{i + 1}"])   # x2, x3, x4
+        r = self._res_chain(g[3], e.body, ws["skip3"], ws["t3"], (ws["a3"], ws["b3"]), tail_split)
+        for i, st in zip((2, 1, 0), e.ups):
+            # x + x4 (then + x3, + x2) is fused into the up-conv's operand load; t{i} holds its output, is the input of the blocks
+            # and, with b, their destination: a is the temporary
+            K.launch_up(g[i + 1], g[i], r, ws[f"skip{i + 1}"], st.stride, nc[i + 1], nc[i], ws[f"t{i}"])
+            r = self._res_chain(g[i], st.blocks, ws[f"t{i}"], ws[f"a{i}"], (ws[f"b{i}"], ws[f"t{i}"]), tail_split)
+        if e.tail_valu is not None:   # m_tail(x + x1)
+            K.conv3x3_tail(g[0], r, e.tail_valu, nc[0], self.out_channels, ws["out"], x2=ws["skip0"])
         else:
-            tl = e["tail"]
-            K.conv3x3(g[0], r, tl.pick(g[0]), tl.cin_p, tl.cout_p, ws["out"], cout_valid=self.out_channels, x2=ws["skip0"])
+            K.conv3x3(g[0], r, e.tail.pick(g[0]), e.tail.cin_p, e.tail.cout_p, ws["out"], cout_valid=self.out_channels, x2=ws["skip0"])
         y = out if out is not None else torch.empty((B, self.out_channels, H, W), device=dev, dtype=torch.float32)
         K.unpack_output(g[0], ws["out"], self.out_channels, y)
         return y
-
-    def _res_chain_from_t(self, g, blocks, t_in, a, b):
-        """ResBlocks whose input lives in the `t` buffer: rotate roles so nothing is clobbered."""
-        cur, tmp, other = t_in, a, b
-        for (pk1, pk2) in blocks:
-            self._res_block(g, pk1, pk2, cur, tmp, other)
-            cur, other = other, cur
-        return cur

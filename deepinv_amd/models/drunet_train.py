@@ -65,6 +65,13 @@ def _conv3(g, w, x, relu=False, res1=None, fp32=False, flip=False, gate=None):
     return y
 
 
+def _stride_packs(w, up, fp32):
+    """packs of a 2x2 stride-2 filter, cached per weight tensor and version: the bf16-split kernel where the shapes allow it, the
+    direct kernel with `fp32`"""
+    precision = None if fp32 else "bf16split"
+    return K.cached_pack(("s2", up, precision), w, lambda: K.stride_packs(w, up=up, precision=precision))
+
+
 class Ops2d:
     """what models/unet_autograd.py walks with, for 2-D: activation tensors [C/8, cs, 8] of `K.alloc`, weights zero-padded to
     multiples of 64 channels up front (their gradients are sliced back), the ResBlock / stride-2 / transposed convolutions of the
@@ -111,10 +118,7 @@ class Ops2d:
         gi, go = self.g[i], self.g[i + 1]
         cout, cin = w.shape[:2]
         y = K.alloc(go, cout, x.device)
-        if cin % 16 == 0 and not fp32:
-            K.down2x2_bf16s(gi, go, x, K.cached_pack("dns", w, lambda: K.pack_down_bf16s_weight(w)), cin, cout, y)
-        else:
-            K.down2x2(gi, go, x, K.cached_pack("dnd", w, lambda: K.pack_down_weight(w)), cin, cout, y)
+        K.launch_down(gi, go, x, _stride_packs(w, False, fp32), cin, cout, y)
         return y
 
     def up(self, i, w, x, fp32=False):
@@ -122,10 +126,7 @@ class Ops2d:
         gi, go = self.g[i + 1], self.g[i]
         cin, cout = w.shape[:2]
         y = K.alloc(go, cout, x.device)
-        if cin % 16 == 0 and not fp32:
-            K.up2x2_bf16s(gi, go, x, None, K.cached_pack("ups", w, lambda: K.pack_up_bf16s_weight(w)), cin, cout, y)
-        else:
-            K.up2x2(gi, go, x, None, K.cached_pack("upd", w, lambda: K.pack_up_weight(w)), cin, cout, y)
+        K.launch_up(gi, go, x, None, _stride_packs(w, True, fp32), cin, cout, y)
         return y
 
     @staticmethod

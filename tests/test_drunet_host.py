@@ -139,7 +139,7 @@ def test_res_block_dispatch_even_and_odd_widths(monkeypatch):
     monkeypatch.setattr(D.K, "conv3x3_split", lambda g, x, w, ci, co, y, res1=None, relu=False, x_presplit=False, y_presplit=False,
                         gate=False: calls.append(("split", relu, res1 is not None, x_presplit, y_presplit)))
     model = D.DRUNet.__new__(D.DRUNet)
-    model._conv_fp32 = lambda g, pk, x, y, relu=False, res1=None: calls.append(("fp32", relu, res1 is not None))
+    model._conv_fp32 = lambda g, pk, x, y, relu=False, res1=None, tail_split=True: calls.append(("fp32", relu, res1 is not None))
     pk = D.K.ConvPacks(None, None, 64, 64, split2d="s2d", wsplit="wsp")
     x = t = y = object()
     model._res_block(types.SimpleNamespace(width=40), pk, pk, x, t, y)

@@ -562,6 +562,41 @@ def test_drunet_batch_lanes_are_reproducible(dev, precision):
         H._LANE_STREAMS.update(saved)
 
 
+def test_drunet_lane_is_the_explicit_tail_split_argument(dev):
+    """What a batch lane runs with is `_hip_forward_lane(..., tail_split=False)` and nothing else (no state of the model): two
+    lanes on their streams return the bits of the same two calls made one after the other on the current stream by another model
+    instance with the same weights.  At 128 x 128 a unit has 32 level-0 workgroup tiles of the F(4x4) kernel, so a lane of
+    ceil(CUs / 32) units is the smallest whose level-0 launches have no fewer tiles than compute units - where `tail_split`
+    changes a launch (no workspace) and with it the summation order: against the whole batch in one sequence, to 1e-5 only."""
+    import copy
+    import deepinv_amd as dinv
+    import deepinv_amd.hip as H
+    from oracle import drunet_cpu as OD
+
+    per_lane = -(-torch.cuda.get_device_properties(dev).multi_processor_count // 32)
+    B = 2 * per_lane
+    if B > 32:
+        pytest.skip(f"a lane of {per_lane} units at 128 x 128 is more than this test is meant to run")
+    den = dinv.models.DRUNet(3, 3, pretrained=None).to(dev).eval()
+    den.load_state_dict(OD.init_state_dict(3, 3, seed=5))
+    twin = copy.deepcopy(den)
+    x = torch.rand(B, 3, 128, 128, generator=torch.Generator().manual_seed(4)).to(dev)
+    key, saved = H.lane_key(dev, 2), dict(H._LANE_STREAMS)
+    try:
+        H._LANE_STREAMS[key] = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]      # lanes whatever the timing calibration says
+        with torch.no_grad():
+            den.batch_lanes = 2
+            out = den(x, 0.1)
+            parts = torch.cat([twin._hip_forward_lane(x[b0:b1], 0.1, lane=i, tail_split=False)
+                               for i, (b0, b1) in enumerate(H.split_batch(B, 2))])
+            whole = twin._hip_forward_lane(x, 0.1)
+        assert torch.equal(out, parts), f"max difference {float((out - parts).abs().max()):.3e}"
+        assert float((out - whole).norm() / whole.norm()) < 1e-5
+    finally:
+        H._LANE_STREAMS.clear()
+        H._LANE_STREAMS.update(saved)
+
+
 def test_lane_streams_are_calibrated_by_timing(dev):
     """DRUNet._calibrated_lane_streams: the streams of the batch lanes are chosen once per process by timing the real launch
     sequence (two lanes on one HIP hardware queue run one after the other and lose); the decision is cached per device, a set that

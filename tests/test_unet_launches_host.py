@@ -9,6 +9,7 @@ number that comes back means the SAME memory was handed out again (the recycled 
 held one layer longer shows up as another number).
 
 Also here: SHA-256 of the bytes of every bf16-split weight pack of one fixed weight."""
+import functools
 import hashlib
 import json
 import os
@@ -131,7 +132,8 @@ def _infer3d_presplit():
     return run
 
 
-def _infer2d(precision):
+def _infer2d(precision, shape=(1, 2, 32, 40), **lane):
+    """`lane`: the keywords a batch lane passes to `_hip_forward_lane` (lane, out, tail_split)"""
     import deepinv_amd as dinv
 
     model = dinv.models.DRUNet(2, 2, pretrained=None)
@@ -139,21 +141,27 @@ def _infer2d(precision):
 
     def run():
         with torch.no_grad():
-            model._hip_forward_lane(_xin(1, 2, 32, 40).detach(), 0.1)
+            model._hip_forward_lane(_xin(*shape).detach(), 0.1, **lane)
     return run
 
 
-def _dncnn(train):
+# 8 x 128 x 128: 256 x 1, 64 x 2, 16 x 4 and 4 x 8 workgroup tiles (32 tile positions x 64 couts) at the four levels - every ResBlock
+# convolution reaches the F(4x4) kernel (WINOGRAD4_MIN_TILES = 32), and level 0 alone has as many tiles as the 256 compute units
+# that `_compute_units` answers for a CPU device
+WINO4_SHAPE = (8, 2, 128, 128)
+
+
+def _dncnn(train, shape=(1, 2, 16, 16), **arch):
     import deepinv_amd as dinv
     from deepinv_amd.models import dncnn
 
-    model = dinv.models.DnCNN(2, 2, depth=5, nf=64, pretrained=None)
+    model = dinv.models.DnCNN(shape[1], shape[1], pretrained=None, **{"depth": 5, "nf": 64, **arch})
     if train:
-        return lambda: dncnn.DnCNNFunction.apply(model, _xin(1, 2, 16, 16), *model.parameters()).sum().backward()
+        return lambda: dncnn.DnCNNFunction.apply(model, _xin(*shape), *model.parameters()).sum().backward()
 
     def run():
         with torch.no_grad():
-            model._hip_forward(_xin(1, 2, 16, 16).detach())
+            model._hip_forward(_xin(*shape).detach())
     return run
 
 
@@ -166,9 +174,15 @@ CASES = {
     "infer2d_split": lambda: _infer2d("bf16split"),
     "dncnn_infer": lambda: _dncnn(False),
     "dncnn_train": lambda: _dncnn(True),
+    "infer2d_wino4": lambda: _infer2d("fp32", WINO4_SHAPE),
+    "infer2d_wino4_lane": lambda: _infer2d("fp32", WINO4_SHAPE, tail_split=False),
+    "infer2d_lane1": lambda: _infer2d("fp32", lane=1, out=torch.empty(1, 2, 32, 40)),
+    "dncnn_infer_nobias": lambda: _dncnn(False, bias=False),
+    "dncnn_infer_thin": lambda: _dncnn(False, (1, 5, 16, 20), depth=4, nf=32),
 }
 
 
+@functools.lru_cache(maxsize=None)
 def trace(case):
     torch.manual_seed(0)
     return record(CASES[case]())
@@ -183,6 +197,44 @@ def test_launch_trace_matches_golden(case):
     assert [l[0] for l in got] == [l[0] for l in want], "another sequence of entry points"
     for i, (a, b) in enumerate(zip(got, want)):
         assert a == b, f"launch {i}: {a} != {b}"
+
+
+def _wino4_workspaces(case):
+    """{image height: [workspace argument, ...]} of the F(4x4) launches of a case"""
+    by_level = {}
+    for name, args in trace(case):
+        if name == "dinv_conv3x3_winograd4":
+            assert (args[8] is None) == (args[9] == 0)
+            by_level.setdefault(args[0][2], []).append(args[8])
+    return by_level
+
+
+def test_wino4_cases_reach_the_kernel_and_the_tail_split_rule():
+    """what the two 8 x 128 x 128 cases are there to pin: all 56 ResBlock convolutions run on the F(4x4) kernel; with the tail split
+    every launch has the workspace, without it (a batch lane) only the launches of fewer tiles than compute units: level 0 has 256
+    tiles on 256 units and gets none, levels 1 to 3 have 128, 64 and 32 and keep it"""
+    whole, lane = _wino4_workspaces("infer2d_wino4"), _wino4_workspaces("infer2d_wino4_lane")
+    for by_level in (whole, lane):
+        assert {h: len(v) for h, v in by_level.items()} == {128: 16, 64: 16, 32: 16, 16: 8}
+    assert all(w is not None for v in whole.values() for w in v)
+    assert all(w is None for w in lane[128])
+    assert all(w is not None for h in (64, 32, 16) for w in lane[h])
+
+
+def test_forward_writes_no_model_state():
+    """the launch policy of a call travels as an argument: a forward call leaves no attribute on the model but the engine cache"""
+    import deepinv_amd as dinv
+
+    assert not hasattr(dinv.models.DRUNet, "_tail_split")
+    drunet = dinv.models.DRUNet(2, 2, nc=(16, 32, 64, 64), nb=1, pretrained=None)
+    dncnn = dinv.models.DnCNN(2, 2, depth=3, nf=64, pretrained=None)
+    x = _xin(1, 2, 32, 32).detach()
+    for model, run in ((drunet, lambda: drunet._hip_forward_lane(x, 0.1, lane=1, tail_split=False)), (dncnn, lambda: dncnn._hip_forward(x))):
+        before = set(vars(model))
+        with torch.no_grad():
+            assert len(record(run)) > 0
+        assert set(vars(model)) - before <= {"_engine"} and before <= set(vars(model))
+        assert not hasattr(model, "_tail_split")
 
 
 # ---- packs: bytes of every bf16-split pack of one fixed weight
