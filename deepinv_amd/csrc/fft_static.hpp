@@ -128,7 +128,7 @@ struct TileFft {
 
     // LDS_IN: the inputs themselves live in `buf` (natural order, whatever addressing `load` uses): every thread first
     // pulls ALL its stage-1 inputs into registers, then the workgroup synchronises, and only then are the stage-1
-    // outputs written over the same LDS tile (two transforms back to back on one tile, see mri_cols_normal_kernel).
+    // outputs written over the same LDS tile (the tile the caller staged them in, see mri_cols_expand_fwd_kernel).
     // stage-1 inputs of this thread pulled into registers by the caller (software pipelining across tiles: the loads of
     // the NEXT tile are in flight while the current one is transformed); feed them back through run_regs()
     template <class LoadF>

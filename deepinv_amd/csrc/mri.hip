@@ -7,11 +7,27 @@
 // scaling, the mask multiply and the coil reduction are folded into the load/store phases
 // of the FFT passes, so the tensor makes one HBM round trip per transformed axis.
 //
-//   forward 2-D : rows(W)  [x,S -> t]          ; cols(H) [t -> y*mask]
-//   forward 3-D : rows(W)  [x,S -> t]          ; cols(H) [t -> t] ; cols(D) [t -> y*mask]
-//   adjoint 2-D : cols(H)  [y*mask -> t]       ; rows(W)+coil-combine [t,S -> x]
-//   adjoint 3-D : cols(D)  [y*mask -> t]       ; cols(H) [t -> t] ; rows(W)+combine
 // t is a complex64 scratch of B*N*vol elements supplied by the caller.
+//
+// The entry points (A = dinv_mri_forward, A^T = dinv_mri_adjoint, A^T A = dinv_mri_normal) open one call context (open_call:
+// every check, every derived size) and run the passes of one pipeline; the passes are the functions under "host side" below.
+// axis0 = first volume axis, W = last (contiguous) axis, mid_axis = the middle axis of a 3-D volume (skipped in 2-D).
+//
+//   wave    (wave2d_ok, mri_wave.hpp: 2-D, H and W in {256, 320, 512}; A^T and A^T A from B * 64 >= 1024)
+//     A     : rows_dif [x,S -> t] ; cols64 [t -> y*mask]
+//     A^T   : rows_dif^-1 [y*mask -> t] ; cols64_combine [t,S -> x]
+//     A^T A : rows_dif [x,S -> t] ; cols64 [F, M^2, F^-1 on t] ; rows_combine [t,S -> x]
+//   static  (all_static: a static plan on every axis, W >= 64; for A^T A normal_ok, and no other pipeline but wave)
+//     A     : expand_axis0 [x,S -> t] ; mid_axis ; rows_mask_store [t -> y*mask]
+//     A^T   : rows_mask_load [y*mask -> t] ; mid_axis^-1 ; combine_axis0 [t,S -> x]
+//     A^T A : expand_axis0 [x,S -> t] ; mid_axis ; rows_normal [F, M^2, F^-1 on t] ; mid_axis^-1 ; combine_axis0 [t,S -> x]
+//   generic (every other size)
+//     A     : rows_coil_load [x,S -> t] ; mid_axis ; cols_mask_store [t -> y*mask]
+//     A^T   : cols_mask_load [y*mask -> t] ; mid_axis^-1 ; rows_combine [t,S -> x]
+//
+// The static order touches the big planar k-space tensor y only along its contiguous rows, and reads x / the coil maps once
+// per workgroup instead of once per coil / batch element.  A^T A never forms y: 2-D, 4 passes over t instead of the 10 of
+// A followed by A^T (which also write and re-read y); it is what L2.grad / CG call every iteration.
 #include "fft_core.hpp"
 #include "fft_launch.hpp"
 
@@ -52,6 +68,52 @@ struct RowsCoilLoadIo {
     __host__ void set_geometry(int64_t n, int64_t q) { n_ = n; q_ = q; }
 };
 
+// ---- address arithmetic the planar k-space Io structs below share (each is a kernel argument: own fields, free helpers).
+// Element offsets of image p = b * ncoil + n, `o` elements into its volume: t [B*N,vol], the re / im planes of y [B,2,N,vol], mask
+struct PlanarCtx { int64_t t, yre, yim, mre, mim; };
+__device__ __forceinline__ PlanarCtx planar_ctx(int64_t p, int64_t o, int64_t vol, int32_t ncoil, int32_t mask_batch) {
+    const int64_t b = p / ncoil, n = p % ncoil;
+    PlanarCtx c;
+    c.t = p * vol + o;
+    c.yre = ((b * 2) * ncoil + n) * vol + o;
+    c.yim = c.yre + (int64_t)ncoil * vol;
+    c.mre = ((mask_batch > 1 ? b : 0) * 2) * vol + o;
+    c.mim = c.mre + vol;
+    return c;
+}
+// the same for row `line` of the [B*N*R, W] view
+__device__ __forceinline__ PlanarCtx planar_row_ctx(int64_t line, int64_t R, int64_t W, int32_t ncoil, int32_t mask_batch) {
+    const int64_t r = line % R, bn = line / R;
+    const int64_t n = bn % ncoil, b = bn / ncoil;
+    const int64_t vol = R * W;
+    PlanarCtx c;
+    c.t = line * W;
+    c.yre = ((b * 2) * ncoil + n) * vol + r * W;
+    c.yim = c.yre + (int64_t)ncoil * vol;
+    c.mre = ((mask_batch > 1 ? b : 0) * 2) * vol + r * W;
+    c.mim = c.mre + vol;
+    return c;
+}
+// wave-autonomous rows pass (fft_wave.hpp): a tile of LW consecutive rows lies inside one (b, n) image, lanes add a 32-bit offset
+// to wave-uniform bases.  (The two tile_ctx and two mask multiplies stay written out: as helpers they changed their kernels' code.)
+inline bool planar_wave_rows_ok(int64_t R, int64_t W, int lw, int64_t nlines) {
+    return R % lw == 0 && (uint64_t)R * (uint64_t)W < (1ull << 31) && nlines < (1ll << 31);
+}
+// the float multiply by the mask, exactly as mri.py:271 does it (re and im planes have masks of their own)
+__device__ __forceinline__ float2 mask_mul(const float* mask, int64_t mre, int64_t mim, float2 v) {
+    v.x = mask[mre] * v.x;
+    v.y = mask[mim] * v.y;
+    return v;
+}
+__device__ __forceinline__ void mask_mul4(const float4& mr, const float4& mi, float4& re, float4& im) {
+    re = make_float4(mr.x * re.x, mr.y * re.y, mr.z * re.z, mr.w * re.w);
+    im = make_float4(mi.x * im.x, mi.y * im.y, mi.z * im.z, mi.w * im.w);
+}
+__device__ __forceinline__ void interleave4(const float4 re, const float4 im, float2 (&v)[4]) {
+    v[0] = make_float2(re.x, im.x); v[1] = make_float2(re.y, im.y);
+    v[2] = make_float2(re.z, im.z); v[3] = make_float2(re.w, im.w);
+}
+
 // ---- last cols pass of the forward op: interleaved t -> planar y times mask
 struct ColsPlanarMaskStoreIo {
     const float2* t;    // [P=B*N, Na, Q]
@@ -60,19 +122,9 @@ struct ColsPlanarMaskStoreIo {
     int32_t ncoil, mask_batch;
     int64_t n_, q_;
     struct RowCtx {};
-    struct ColCtx { int64_t tin, yre, yim, mre, mim; };
-    __device__ __forceinline__ ColCtx col_ctx(int64_t p, int64_t q) const {
-        const int64_t vol = n_ * q_;
-        const int64_t b = p / ncoil, n = p % ncoil;
-        ColCtx c;
-        c.tin = p * vol + q;
-        c.yre = ((b * 2) * ncoil + n) * vol + q;
-        c.yim = c.yre + (int64_t)ncoil * vol;
-        c.mre = ((mask_batch > 1 ? b : 0) * 2) * vol + q;
-        c.mim = c.mre + vol;
-        return c;
-    }
-    __device__ __forceinline__ float2 load(const ColCtx& c, int k) const { return t[c.tin + (int64_t)k * q_]; }
+    using ColCtx = PlanarCtx;
+    __device__ __forceinline__ ColCtx col_ctx(int64_t p, int64_t q) const { return planar_ctx(p, q, n_ * q_, ncoil, mask_batch); }
+    __device__ __forceinline__ float2 load(const ColCtx& c, int k) const { return t[c.t + (int64_t)k * q_]; }
     __device__ __forceinline__ void store(const ColCtx& c, int k, float2 v) const {
         const int64_t o = (int64_t)k * q_;
         if (mask) {
@@ -95,28 +147,15 @@ struct ColsPlanarMaskLoadIo {
     int32_t ncoil, mask_batch;
     int64_t n_, q_;
     struct RowCtx {};
-    struct ColCtx { int64_t tout, yre, yim, mre, mim; };
-    __device__ __forceinline__ ColCtx col_ctx(int64_t p, int64_t q) const {
-        const int64_t vol = n_ * q_;
-        const int64_t b = p / ncoil, n = p % ncoil;
-        ColCtx c;
-        c.tout = p * vol + q;
-        c.yre = ((b * 2) * ncoil + n) * vol + q;
-        c.yim = c.yre + (int64_t)ncoil * vol;
-        c.mre = ((mask_batch > 1 ? b : 0) * 2) * vol + q;
-        c.mim = c.mre + vol;
-        return c;
-    }
+    using ColCtx = PlanarCtx;
+    __device__ __forceinline__ ColCtx col_ctx(int64_t p, int64_t q) const { return planar_ctx(p, q, n_ * q_, ncoil, mask_batch); }
     __device__ __forceinline__ float2 load(const ColCtx& c, int k) const {
         const int64_t o = (int64_t)k * q_;
         float2 v = make_float2(y[c.yre + o], y[c.yim + o]);
-        if (mask) {
-            v.x = mask[c.mre + o] * v.x;
-            v.y = mask[c.mim + o] * v.y;
-        }
+        if (mask) v = mask_mul(mask, c.mre + o, c.mim + o, v);
         return v;
     }
-    __device__ __forceinline__ void store(const ColCtx& c, int k, float2 v) const { t[c.tout + (int64_t)k * q_] = v; }
+    __device__ __forceinline__ void store(const ColCtx& c, int k, float2 v) const { t[c.t + (int64_t)k * q_] = v; }
     __host__ void set_geometry(int64_t n, int64_t q) { n_ = n; q_ = q; }
 };
 
@@ -266,13 +305,7 @@ int launch_combine_static(const float2* t, const float2* maps, float* x, int64_t
     return 0;
 }
 
-// =====================================================================================================
-// Static-plan pipeline (all transformed sizes in {16,32,64,128,256,320,512}): pass order chosen so that the big
-// planar k-space tensor y is only ever touched along its contiguous rows, and x / coil maps are read once per
-// workgroup instead of once per coil / batch element:
-//   forward : cols(first axis) with coil loop [x cached in registers, S -> t] ; (cols(H) in place) ; rows(W) [t -> y*mask]
-//   adjoint : rows(W) [y*mask -> t] ; (cols(H) in place) ; cols(first axis) + coil combine [t,S -> x]
-// =====================================================================================================
+// ================================ static pipeline (every size in {16,32,64,128,256,320,512}; pass order: the table at the top)
 
 // rows pass, forward: interleaved t -> planar y * mask   (lines = (b, n, r) rows of length W)
 struct RowsPlanarMaskStoreIo {
@@ -283,44 +316,24 @@ struct RowsPlanarMaskStoreIo {
     int32_t ncoil, mask_batch;
     int64_t R, W;  // rows per volume, row length
     int64_t n_, q_;
-    struct RowCtx { int64_t tin, yre, yim, mre, mim; };
+    using RowCtx = PlanarCtx;
     struct ColCtx {};
-    __device__ __forceinline__ RowCtx row_ctx(int64_t line) const {
-        const int64_t r = line % R, bn = line / R;
-        const int64_t n = bn % ncoil, b = bn / ncoil;
-        const int64_t vol = R * W;
-        RowCtx c;
-        c.tin = line * W;
-        c.yre = ((b * 2) * ncoil + n) * vol + r * W;
-        c.yim = c.yre + (int64_t)ncoil * vol;
-        c.mre = ((mask_batch > 1 ? b : 0) * 2) * vol + r * W;
-        c.mim = c.mre + vol;
-        return c;
-    }
-    __device__ __forceinline__ float2 load(const RowCtx& c, int n) const { return t[c.tin + n]; }
+    __device__ __forceinline__ RowCtx row_ctx(int64_t line) const { return planar_row_ctx(line, R, W, ncoil, mask_batch); }
+    __device__ __forceinline__ float2 load(const RowCtx& c, int n) const { return t[c.t + n]; }
     __device__ __forceinline__ void store(const RowCtx& c, int k, float2 v) const {
-        if (mask) {  // float multiply exactly as mri.py:271; masked-out samples are written as exact zeros
-            v.x = mask[c.mre + k] * v.x;
-            v.y = mask[c.mim + k] * v.y;
-        }
+        if (mask) v = mask_mul(mask, c.mre + k, c.mim + k, v);  // masked-out samples are written as exact zeros
         y[c.yre + k] = v.x;
         y[c.yim + k] = v.y;
     }
     static constexpr bool has_vec4 = true;
-    __device__ __forceinline__ void load4(const RowCtx& c, int n0, float2 (&v)[4]) const { ld_c4(t + c.tin + n0, v); }
+    __device__ __forceinline__ void load4(const RowCtx& c, int n0, float2 (&v)[4]) const { ld_c4(t + c.t + n0, v); }
     __device__ __forceinline__ void store4(const RowCtx& c, int k0, const float2 (&v)[4]) const {
         float4 re = make_float4(v[0].x, v[1].x, v[2].x, v[3].x), im = make_float4(v[0].y, v[1].y, v[2].y, v[3].y);
-        if (mask) {
-            const float4 mr = ld_f4(mask + c.mre + k0), mi = ld_f4(mask + c.mim + k0);
-            re = make_float4(mr.x * re.x, mr.y * re.y, mr.z * re.z, mr.w * re.w);
-            im = make_float4(mi.x * im.x, mi.y * im.y, mi.z * im.z, mi.w * im.w);
-        }
+        if (mask) mask_mul4(ld_f4(mask + c.mre + k0), ld_f4(mask + c.mim + k0), re, im);
         st_f4(y + c.yre + k0, re);
         st_f4(y + c.yim + k0, im);
     }
-    // wave-autonomous rows pass (fft_wave.hpp): a tile of LW consecutive rows must lie inside one (b, n) image; its base
-    // pointers are wave-uniform, lanes add a 32-bit element offset
-    __host__ bool wave_rows_ok(int lw, int64_t nlines) const { return R % lw == 0 && (uint64_t)R * (uint64_t)W < (1ull << 31) && nlines < (1ll << 31); }
+    __host__ bool wave_rows_ok(int lw, int64_t nlines) const { return planar_wave_rows_ok(R, W, lw, nlines); }
     struct Raw4 { float4 a, b; };
     struct TileCtx { const float2* tin; float* yre; float* yim; const float* mre; const float* mim; };
     __device__ __forceinline__ TileCtx tile_ctx(int64_t line0) const {      // (32-bit divisions: wave_rows_ok bounds the sizes)
@@ -342,11 +355,7 @@ struct RowsPlanarMaskStoreIo {
     }
     __device__ __forceinline__ void store4(const TileCtx& c, unsigned off, const float2 (&v)[4]) const {
         float4 re = make_float4(v[0].x, v[1].x, v[2].x, v[3].x), im = make_float4(v[0].y, v[1].y, v[2].y, v[3].y);
-        if (mask) {  // float multiply exactly as mri.py:271; masked-out samples are written as exact zeros
-            const float4 mr = ld_f4(c.mre + off), mi = ld_f4(c.mim + off);
-            re = make_float4(mr.x * re.x, mr.y * re.y, mr.z * re.z, mr.w * re.w);
-            im = make_float4(mi.x * im.x, mi.y * im.y, mi.z * im.z, mi.w * im.w);
-        }
+        if (mask) mask_mul4(ld_f4(c.mre + off), ld_f4(c.mim + off), re, im);
         st_f4(c.yre + off, re);
         st_f4(c.yim + off, im);
     }
@@ -361,43 +370,24 @@ struct RowsPlanarMaskLoadIo {
     int32_t ncoil, mask_batch;
     int64_t R, W;
     int64_t n_, q_;
-    struct RowCtx { int64_t tout, yre, yim, mre, mim; };
+    using RowCtx = PlanarCtx;
     struct ColCtx {};
-    __device__ __forceinline__ RowCtx row_ctx(int64_t line) const {
-        const int64_t r = line % R, bn = line / R;
-        const int64_t n = bn % ncoil, b = bn / ncoil;
-        const int64_t vol = R * W;
-        RowCtx c;
-        c.tout = line * W;
-        c.yre = ((b * 2) * ncoil + n) * vol + r * W;
-        c.yim = c.yre + (int64_t)ncoil * vol;
-        c.mre = ((mask_batch > 1 ? b : 0) * 2) * vol + r * W;
-        c.mim = c.mre + vol;
-        return c;
-    }
+    __device__ __forceinline__ RowCtx row_ctx(int64_t line) const { return planar_row_ctx(line, R, W, ncoil, mask_batch); }
     __device__ __forceinline__ float2 load(const RowCtx& c, int n) const {
         float2 v = make_float2(y[c.yre + n], y[c.yim + n]);
-        if (mask) {
-            v.x = mask[c.mre + n] * v.x;
-            v.y = mask[c.mim + n] * v.y;
-        }
+        if (mask) v = mask_mul(mask, c.mre + n, c.mim + n, v);
         return v;
     }
-    __device__ __forceinline__ void store(const RowCtx& c, int k, float2 v) const { t[c.tout + k] = v; }
+    __device__ __forceinline__ void store(const RowCtx& c, int k, float2 v) const { t[c.t + k] = v; }
     static constexpr bool has_vec4 = true;
     __device__ __forceinline__ void load4(const RowCtx& c, int n0, float2 (&v)[4]) const {
         float4 re = ld_f4(y + c.yre + n0), im = ld_f4(y + c.yim + n0);
-        if (mask) {
-            const float4 mr = ld_f4(mask + c.mre + n0), mi = ld_f4(mask + c.mim + n0);
-            re = make_float4(mr.x * re.x, mr.y * re.y, mr.z * re.z, mr.w * re.w);
-            im = make_float4(mi.x * im.x, mi.y * im.y, mi.z * im.z, mi.w * im.w);
-        }
-        v[0] = make_float2(re.x, im.x); v[1] = make_float2(re.y, im.y);
-        v[2] = make_float2(re.z, im.z); v[3] = make_float2(re.w, im.w);
+        if (mask) mask_mul4(ld_f4(mask + c.mre + n0), ld_f4(mask + c.mim + n0), re, im);
+        interleave4(re, im, v);
     }
-    __device__ __forceinline__ void store4(const RowCtx& c, int k0, const float2 (&v)[4]) const { st_c4(t + c.tout + k0, v); }
+    __device__ __forceinline__ void store4(const RowCtx& c, int k0, const float2 (&v)[4]) const { st_c4(t + c.t + k0, v); }
     // wave-autonomous rows pass (fft_wave.hpp): the mask multiply happens when the registers are consumed
-    __host__ bool wave_rows_ok(int lw, int64_t nlines) const { return R % lw == 0 && (uint64_t)R * (uint64_t)W < (1ull << 31) && nlines < (1ll << 31); }
+    __host__ bool wave_rows_ok(int lw, int64_t nlines) const { return planar_wave_rows_ok(R, W, lw, nlines); }
     struct Raw4 { float4 re, im; };
     struct TileCtx { float2* tout; const float* yre; const float* yim; const float* mre; const float* mim; };
     __device__ __forceinline__ TileCtx tile_ctx(int64_t line0) const {      // (32-bit divisions: wave_rows_ok bounds the sizes)
@@ -425,8 +415,7 @@ struct RowsPlanarMaskLoadIo {
             re = make_float4(m.mr.x * re.x, m.mr.y * re.y, m.mr.z * re.z, m.mr.w * re.w);
             im = make_float4(m.mi.x * im.x, m.mi.y * im.y, m.mi.z * im.z, m.mi.w * im.w);
         }
-        v[0] = make_float2(re.x, im.x); v[1] = make_float2(re.y, im.y);
-        v[2] = make_float2(re.z, im.z); v[3] = make_float2(re.w, im.w);
+        interleave4(re, im, v);
     }
     __device__ __forceinline__ void store4(const TileCtx& c, unsigned off, const float2 (&v)[4]) const { st_c4(c.tout + off, v); }
     __host__ void set_geometry(int64_t n, int64_t q) { n_ = n; q_ = q; }
@@ -539,12 +528,11 @@ __global__ __launch_bounds__(NT) void mri_cols_combine_inv_kernel(const float2* 
                                                                   const void* table, float scale) {
     using TF = TileFft<P, true, false, L, NT>;
     constexpr int N = P::N;
-    __shared__ __attribute__((aligned(16))) float2 buf[P::STAGES > 1 ? TF::lds_floats2 : 1];
-    const float2* tw = reinterpret_cast<const float2*>(table);
+    // depth 16 only (combine_axis0): one butterfly in registers, so no LDS tile, no twiddle table (`table` is unused), no barrier
+    static_assert(P::STAGES == 1, "the fused inverse + coil combination is a single-stage pass");
     const int tid = threadIdx.x, line = tid % L;
     const int c = N / 2;
     const int64_t vol = (int64_t)N * Q;
-    constexpr int Q2N = (P::STAGES == 3) ? P::R2 : 1;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t b = tile / qtiles;
         const int64_t q0 = (tile - b * qtiles) * L;
@@ -555,10 +543,12 @@ __global__ __launch_bounds__(NT) void mri_cols_combine_inv_kernel(const float2* 
         for (int a = 0; a < TF::NSL; ++a)
 #pragma unroll
             for (int r = 0; r < TF::RL; ++r) acc[a][r] = make_float2(0.f, 0.f);
-        // output position k of (slot, r): the last-stage item decomposition of TileFft::run
+        // output position k of register r: the single stage of TileFft::run emits k = r, centred.  (w and i are what is left of
+        // the multi-stage item decomposition; the compiler drops them, but the kernel's code changes when the source does)
         auto out_k = [&](int slot, int r) {
             const int w = tid + NT * slot, i = w / L;
-            int k = (P::STAGES == 1 ? r : (i % P::R1) + P::R1 * (i / P::R1) + P::R1 * Q2N * r) + c;
+            (void)i;
+            int k = r + c;
             return k >= N ? k - N : k;
         };
         // two register sets (A, B) alternate: the loads of coil n + 1 are in flight while coil n is transformed
@@ -571,8 +561,7 @@ __global__ __launch_bounds__(NT) void mri_cols_combine_inv_kernel(const float2* 
 #define DINV_XFORM(coil, V)                                                                                           \
         do {                                                                                                          \
             const float2* s_ = maps ? maps + (((maps_batch > 1 ? b : 0) * ncoil + (coil)) * vol + q) : nullptr;       \
-            if (P::STAGES > 1) __syncthreads(); /* the previous transform has left the LDS tile */                    \
-            TF::run_regs(buf, tw, cols, c, scale, tid, V, [&](int slot, int, int k, int r, float2 v) {                \
+            TF::run_regs(nullptr, nullptr, cols, c, scale, tid, V, [&](int slot, int, int k, int r, float2 v) {       \
                 if (s_) v = cmulc(v, s_[(int64_t)k * Q]); /* conj(S) * v */                                           \
                 acc[slot][r] = cadd(acc[slot][r], v);                                                                 \
             });                                                                                                       \
@@ -673,23 +662,19 @@ __global__ __launch_bounds__(256) void mri_coil_combine_any_kernel(const float2*
 template <int N>
 int launch_cols_expand_fwd(const float* x, const float2* maps, float2* t, int64_t B, int ncoil, int maps_batch, int64_t Q,
                            const void* table, float scale, hipStream_t s) {
-    using P = typename PlanFor<N>::P;
-    if constexpr (P::STAGES > 1) {
-        constexpr int L = ColsL<N>::value;
-        const int64_t qtiles = ceil_div(Q, L), nsets = B * qtiles;
-        const int64_t padded = ceil_div(nsets, 8) * 8 * ncoil;
-        const unsigned grid = (unsigned)std::min<int64_t>(padded, 4 * kMaxGrid);
-        // 256 threads: two workgroups per CU at N = 320 (210 VGPRs), so one tile's loads overlap another's transform
-        // (measured at cfg2: 111 us; 512 threads / 148 VGPRs = one workgroup per CU: 135 us; 512 threads capped at 128
-        // VGPRs (spills): 171 us)
-        constexpr int NT = 256;
-        hipLaunchKernelGGL((mri_cols_expand_fwd_kernel<P, L, NT>), dim3(grid), dim3(NT), 0, s, x, maps, t, ncoil, maps_batch, Q,
-                           qtiles, nsets, table, scale);
-        DINV_CHECK_LAUNCH();
-        return 0;
-    } else {
-        return fail(2, "no fused expand pass for length %d", N);
-    }
+    using P = typename PlanFor<N>::P;   // (multi-stage lengths only: the kernel asserts it)
+    constexpr int L = ColsL<N>::value;
+    const int64_t qtiles = ceil_div(Q, L), nsets = B * qtiles;
+    const int64_t padded = ceil_div(nsets, 8) * 8 * ncoil;
+    const unsigned grid = (unsigned)std::min<int64_t>(padded, 4 * kMaxGrid);
+    // 256 threads: two workgroups per CU at N = 320 (210 VGPRs), so one tile's loads overlap another's transform
+    // (measured at cfg2: 111 us; 512 threads / 148 VGPRs = one workgroup per CU: 135 us; 512 threads capped at 128
+    // VGPRs (spills): 171 us)
+    constexpr int NT = 256;
+    hipLaunchKernelGGL((mri_cols_expand_fwd_kernel<P, L, NT>), dim3(grid), dim3(NT), 0, s, x, maps, t, ncoil, maps_batch, Q,
+                       qtiles, nsets, table, scale);
+    DINV_CHECK_LAUNCH();
+    return 0;
 }
 
 template <int N>
@@ -699,7 +684,7 @@ int launch_cols_combine_inv(const float2* t, const float2* maps, float* x, int64
     constexpr int L = ColsL<N>::value;
     const int64_t qtiles = ceil_div(Q, L), ntiles = B * qtiles;
     const unsigned grid = (unsigned)std::min<int64_t>(ntiles, 4 * kMaxGrid);
-    constexpr int NT = N >= 256 ? 512 : 256;
+    constexpr int NT = 256;
     hipLaunchKernelGGL((mri_cols_combine_inv_kernel<P, L, NT>), dim3(grid), dim3(NT), 0, s, t, maps, x, ncoil, maps_batch, Q,
                        qtiles, ntiles, table, scale);
     DINV_CHECK_LAUNCH();
@@ -708,14 +693,14 @@ int launch_cols_combine_inv(const float2* t, const float2* maps, float* x, int64
 
 // ---- normal operator, middle pass along the LAST (contiguous) axis: t <- F^H_W( M^2 . F_W t ) on tiles of L rows; the forward
 // transform emits masked k-space rows into a second LDS tile in natural order, the inverse transform reads them from
-// there.  This is the variant the normal operator uses.
+// there.
 // Measured at cfg2 (B = 32, 8 coils, 320 x 320; us per pass): expand 52-60 + cols 78 + THIS ~145 + cols^-1 71 + combine 38
 // = 0.389 ms (3-D cfg4 volume pair: 0.493 vs 0.578 ms).  The transforms themselves, not HBM, set the pace of this pass:
 // two of them on one 420 MB round trip take as long as two single-transform passes would.
-// The column variant above needs 171 us for its 420 MB round trip (234 VGPRs) and forces the planar 4-byte rows passes
-// on both ends (116 + 193 us): 0.473 ms in all vs 0.487 ms for dinv_mri_forward + dinv_mri_adjoint.  A first rows
-// variant that kept the forward outputs in registers (one LDS tile, L = 16) ran at 256 VGPRs + 22 AGPRs = one wave per
-// SIMD and took 234 us.
+// An earlier variant that did this along the FIRST axis (columns) needed 171 us for its 420 MB round trip (234 VGPRs) and
+// forced the planar 4-byte rows passes on both ends (116 + 193 us): 0.473 ms in all vs 0.487 ms for dinv_mri_forward +
+// dinv_mri_adjoint.  A first rows variant that kept the forward outputs in registers (one LDS tile, L = 16) ran at
+// 256 VGPRs + 22 AGPRs = one wave per SIMD and took 234 us.
 template <class P, int L>
 __global__ __launch_bounds__(256) void mri_rows_normal_kernel(float2* __restrict__ t, const float* __restrict__ mask,
                                                               int64_t nlines, int64_t R, int ncoil, int mask_batch,
@@ -771,14 +756,7 @@ int launch_rows_normal(float2* t, const float* mask, int64_t nlines, int64_t R, 
     return 0;
 }
 
-#define DINV_ALL_STATIC(X) X(16) X(32) X(64) X(128) X(256) X(320) X(512)
-
-bool all_static(const dinv_mri_desc* d) {
-    for (int i = 0; i < d->ndim; ++i)
-        if (!has_static_plan(d->dims[i])) return false;
-    return d->dims[d->ndim - 1] >= 64;  // the rows pass has static kernels from 64 up
-}
-
+// ================================ host side: the checks and derived sizes of a call, the dispatch predicates, the passes
 int validate(const dinv_mri_desc* d) {
     DINV_REQUIRE(d != nullptr, "null descriptor");
     DINV_REQUIRE(d->ndim == 2 || d->ndim == 3, "ndim must be 2 or 3, got %d", d->ndim);
@@ -802,174 +780,16 @@ inline int64_t volume(const dinv_mri_desc* d) {
     return v;
 }
 
-}  // namespace
-
-extern "C" size_t dinv_mri_workspace_bytes(const dinv_mri_desc* d) {
-    if (!d || d->ndim < 2 || d->ndim > 3) return 0;
-    return (size_t)d->batch * d->coils * volume(d) * sizeof(float2);
+// ---- the dispatch predicates, each said once
+// the static pipeline: every axis has a compile-time plan, and the rows pass has static kernels from 64 up
+bool all_static(const dinv_mri_desc* d) {
+    for (int i = 0; i < d->ndim; ++i)
+        if (!has_static_plan(d->dims[i])) return false;
+    return d->dims[d->ndim - 1] >= 64;
 }
 
-extern "C" int dinv_mri_forward(const dinv_mri_desc* d, const float* x, const float* maps, const float* mask,
-                                float* y, void* workspace, size_t ws_bytes, dinv_stream_t stream) {
-    if (int e = validate(d)) return e;
-    if (d->batch == 0) return 0;
-    DINV_REQUIRE(x && y && workspace, "null tensor pointer");
-    DINV_REQUIRE(ws_bytes >= dinv_mri_workspace_bytes(d), "workspace too small: %zu < %zu", ws_bytes,
-                 dinv_mri_workspace_bytes(d));
-    DINV_REQUIRE((d->maps_batch != 0) == (maps != nullptr), "maps pointer / maps_batch mismatch");
-    DINV_REQUIRE((d->mask_batch != 0) == (mask != nullptr), "mask pointer / mask_batch mismatch");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int nd = d->ndim;
-    const int64_t W = d->dims[nd - 1];
-    const int64_t vol = volume(d);
-    const int64_t R = vol / W;
-    float2* t = reinterpret_cast<float2*>(workspace);
-    const int64_t P = (int64_t)d->batch * d->coils;
-#ifndef DINV_NO_WAVE2D
-    if (mriw::wave2d_ok(d, 0)) return mriw::run_wave2d(d, 0, x, reinterpret_cast<const float2*>(maps), mask, y, t, s);
-#endif
-
-    if (all_static(d)) {
-        const float2* mp = reinterpret_cast<const float2*>(maps);
-        const int64_t N0 = d->dims[0], Q0 = vol / N0;
-        const float sc0 = 1.0f / sqrtf((float)N0);
-        int e = 0;
-        if (Q0 % 4 == 0 && N0 > 16) {
-            // fused first pass: coil expansion + transform along the first axis, t written once
-            switch (d->dims[0]) {
-#define DINV_CASE(NN) case NN: e = launch_cols_expand_fwd<NN>(x, mp, t, d->batch, d->coils, d->maps_batch, Q0, d->table[0], sc0, s); break;
-                DINV_CASE(32) DINV_STATIC_SIZES(DINV_CASE)
-#undef DINV_CASE
-            }
-        } else {
-            // short first axis (a 3-D volume's depth): single-stage transform straight from x and the maps
-            ColsCoilLoadIo cio{x, mp, t, d->coils, d->maps_batch, 0, 0};
-            e = launch_cols(cio, P, Q0, d->plan[0], d->table[0], 0, 1, sc0, s, d->coils);
-        }
-        if (e) return e;
-        if (nd == 3) {
-            C2CIo mio{t, t, 0, 0};
-            if ((e = launch_cols(mio, P * d->dims[0], W, d->plan[1], d->table[1], 0, 1, 1.0f / sqrtf((float)d->dims[1]), s))) return e;
-        }
-        RowsPlanarMaskStoreIo sio{t, y, mask, d->coils, d->mask_batch, R, W, 0, 0};
-        return launch_rows(sio, P * R, d->plan[nd - 1], d->table[nd - 1], 0, 1, 1.0f / sqrtf((float)W), s);
-    }
-    RowsCoilLoadIo rio{x, reinterpret_cast<const float2*>(maps), t, d->coils, d->maps_batch, R, W, 0, 0};
-    if (int e = launch_rows(rio, P * R, d->plan[nd - 1], d->table[nd - 1], 0, 1, 1.0f / sqrtf((float)W), s)) return e;
-    if (nd == 3) {
-        const int64_t H = d->dims[1];
-        C2CIo mio{t, t, 0, 0};
-        if (int e = launch_cols(mio, P * d->dims[0], W, d->plan[1], d->table[1], 0, 1, 1.0f / sqrtf((float)H), s)) return e;
-    }
-    const int64_t Na = d->dims[0];
-    ColsPlanarMaskStoreIo cio{t, y, mask, d->coils, d->mask_batch, 0, 0};
-    return launch_cols(cio, P, vol / Na, d->plan[0], d->table[0], 0, 1, 1.0f / sqrtf((float)Na), s);
-}
-
-extern "C" int dinv_mri_adjoint(const dinv_mri_desc* d, const float* y, const float* maps, const float* mask,
-                                float* x, void* workspace, size_t ws_bytes, dinv_stream_t stream) {
-    if (int e = validate(d)) return e;
-    if (d->batch == 0) return 0;
-    DINV_REQUIRE(x && y && workspace, "null tensor pointer");
-    DINV_REQUIRE(ws_bytes >= dinv_mri_workspace_bytes(d), "workspace too small: %zu < %zu", ws_bytes,
-                 dinv_mri_workspace_bytes(d));
-    DINV_REQUIRE((d->maps_batch != 0) == (maps != nullptr), "maps pointer / maps_batch mismatch");
-    DINV_REQUIRE((d->mask_batch != 0) == (mask != nullptr), "mask pointer / mask_batch mismatch");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int nd = d->ndim;
-    const int64_t W = d->dims[nd - 1];
-    const int64_t vol = volume(d);
-    const int64_t R = vol / W;
-    float2* t = reinterpret_cast<float2*>(workspace);
-    const int64_t P = (int64_t)d->batch * d->coils;
-#ifndef DINV_NO_WAVE2D
-    if (mriw::wave2d_ok(d, 1)) return mriw::run_wave2d(d, 1, y, reinterpret_cast<const float2*>(maps), mask, x, t, s);
-#endif
-
-    if (all_static(d)) {
-        RowsPlanarMaskLoadIo lio{y, mask, t, d->coils, d->mask_batch, R, W, 0, 0};
-        if (int e = launch_rows(lio, P * R, d->plan[nd - 1], d->table[nd - 1], 1, 1, 1.0f / sqrtf((float)W), s)) return e;
-        if (nd == 3) {
-            C2CIo mio{t, t, 0, 0};
-            if (int e = launch_cols(mio, P * d->dims[0], W, d->plan[1], d->table[1], 1, 1, 1.0f / sqrtf((float)d->dims[1]), s)) return e;
-        }
-        const float2* mp = reinterpret_cast<const float2*>(maps);
-        const int64_t N0 = d->dims[0], Q0 = vol / N0;
-        const float sc0 = 1.0f / sqrtf((float)N0);
-        if (vol % 4 == 0 && N0 > 16) {
-            // C2C pass along the first axis in place, then a wide streaming coil combination.  A fused form (one workgroup
-            // walking the coils of a column tile, next coil's loads in flight during the transform) was built in round 3 and
-            // measured 2x slower than these two passes (152 vs 44 + 27 us at cfg2): the serial coil loop leaves too few
-            // independent tiles in flight
-            C2CIo fio{t, t, 0, 0};
-            if (int e = launch_cols(fio, P, Q0, d->plan[0], d->table[0], 1, 1, sc0, s)) return e;
-            const dim3 grid((unsigned)ceil_div(vol / 4, 256), (unsigned)ceil_div(d->batch, CB));
-            hipLaunchKernelGGL((mri_coil_combine_kernel<8>), grid, dim3(256), 0, s, t, mp, x, vol, d->batch, d->coils,
-                               d->maps_batch);
-            DINV_CHECK_LAUNCH();
-            return 0;
-        }
-        // short first axis (a 3-D volume's depth): single-stage inverse transform with the coil sum in its store phase
-        return launch_cols_combine_inv<16>(t, mp, x, d->batch, d->coils, d->maps_batch, Q0, d->table[0], sc0, s);
-    }
-    const dinv_fft_plan& pw = d->plan[nd - 1];
-    // the rows pass below needs no more LDS than the forward's rows pass: refuse here, before anything is written, where that
-    // one refuses too.  (launch_rows' own line-count check, blocks < 2^31, can still refuse after the first pass has written t;
-    // it needs more than 2^31 rows of one length, far past any workspace this operator is given)
-    DINV_REQUIRE(fft_lds_bytes(pw, rows_lines_per_block(pw)) <= kMaxLdsBytes, "fft length %d does not fit the 160 KiB LDS tile",
-                 pw.n);
-    const int64_t Na = d->dims[0];
-    ColsPlanarMaskLoadIo cio{y, mask, t, d->coils, d->mask_batch, 0, 0};
-    if (int e = launch_cols(cio, P, vol / Na, d->plan[0], d->table[0], 1, 1, 1.0f / sqrtf((float)Na), s)) return e;
-    if (nd == 3) {
-        const int64_t H = d->dims[1];
-        C2CIo mio{t, t, 0, 0};
-        if (int e = launch_cols(mio, P * d->dims[0], W, d->plan[1], d->table[1], 1, 1, 1.0f / sqrtf((float)H), s)) return e;
-    }
-    // rows pass + coil combine
-    const float2* mp = reinterpret_cast<const float2*>(maps);
-    {
-        const int64_t nl = (int64_t)d->batch * R;
-        const float sc = 1.0f / sqrtf((float)W);
-        switch (pw.n) {
-#define DINV_CASE(NN) case NN: return launch_combine_static<NN>(t, mp, x, nl, R, d->coils, d->maps_batch, d->table[nd - 1], sc, s);
-            DINV_STATIC_SIZES(DINV_CASE)
-#undef DINV_CASE
-            default: break;
-        }
-    }
-    int lpb = rows_lines_per_block(pw);
-    if (lpb > 16) lpb = 16;
-    const int LS = fft_line_stride(pw.n);
-    const size_t lds = fft_lds_bytes(pw, lpb) + (size_t)lpb * LS * sizeof(float2);
-    if (lds > kMaxLdsBytes) {
-        // the combine tile (FFT tile + an lpb x LS accumulator) does not fit: the in-place inverse rows pass, which has the
-        // forward's LDS limit, then a per-pixel coil combination
-        C2CIo rio{t, t, 0, 0};
-        if (int e = launch_rows(rio, P * R, pw, d->table[nd - 1], 1, 1, 1.0f / sqrtf((float)W), s)) return e;
-        const int64_t total = (int64_t)d->batch * vol;
-        const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(total, 256), 4 * kMaxGrid);
-        hipLaunchKernelGGL(mri_coil_combine_any_kernel, dim3(grid), dim3(256), 0, s, t, mp, x, vol, total, d->coils,
-                           d->maps_batch);
-        DINV_CHECK_LAUNCH();
-        return 0;
-    }
-    if (lds > kDefaultLdsBytes)
-        if (int e = raise_lds_cap<mri_rows_combine_kernel>(kMaxLdsBytes)) return e;
-    const int64_t nlines = (int64_t)d->batch * R;
-    const int64_t blocks = ceil_div(nlines, lpb);
-    hipLaunchKernelGGL(mri_rows_combine_kernel, dim3((unsigned)blocks), dim3(256), lds, s, t, mp, x, nlines, R, d->coils,
-                       d->maps_batch, lpb, pw,
-                       d->table[nd - 1], 1, 1.0f / sqrtf((float)W));
-    DINV_CHECK_LAUNCH();
-    return 0;
-}
-
-// A^T A x without the k-space tensor (what L2.grad / CG call every iteration):
-//   rows(W) [x, S -> t] ; (cols(H) in place) ; cols(first axis): F, M^2, F^H in one LDS tile ; (cols(H)^-1) ;
-//   rows(W)^-1 + coil combine [t, S -> out]
-// 2-D: 4 passes over t instead of the 10 of dinv_mri_forward + dinv_mri_adjoint (which also write and re-read y).
-static bool normal_ok(const dinv_mri_desc* d) {
+// A^T A: the static pipeline with a rows_normal instance for W (DINV_STATIC_SIZES)
+bool normal_ok(const dinv_mri_desc* d) {
     if (!all_static(d)) return false;
     switch (d->dims[d->ndim - 1]) {
 #define DINV_CASE(NN) case NN: return true;
@@ -979,64 +799,241 @@ static bool normal_ok(const dinv_mri_desc* d) {
     }
 }
 
-extern "C" int dinv_mri_normal_supported(const dinv_mri_desc* d) { return d && validate(d) == 0 && normal_ok(d) ? 1 : 0; }
+bool wave_ok(const dinv_mri_desc* d, MriOp op) {
+#ifndef DINV_NO_WAVE2D
+    return mriw::wave2d_ok(d, op);
+#else
+    return false;
+#endif
+}
 
-extern "C" int dinv_mri_normal(const dinv_mri_desc* d, const float* x, const float* maps, const float* mask, float* out,
-                               void* workspace, size_t ws_bytes, dinv_stream_t stream) {
+enum Pipeline { kWave, kStatic, kGeneric };
+
+// ---- one call: what the three entry points check, in their order, and the sizes every pass works with
+struct MriCall {
+    const dinv_mri_desc* d;
+    bool empty;               // batch == 0: nothing to launch
+    Pipeline pipeline;
+    hipStream_t s;
+    int nd;
+    int64_t W, vol, R, P, N0, Q0;   // row length, volume, rows per volume (vol / W), images B * N, first axis, vol / N0
+    float2* t;                // the workspace, [B, N, vol] interleaved
+    const float2* maps;
+    const float* mask;
+    float sc[3];              // 1 / sqrt(dims[i]): every pass scales its own axis
+    const dinv_fft_plan& plan_w() const { return d->plan[nd - 1]; }
+    const void* table_w() const { return d->table[nd - 1]; }
+    float sc_w() const { return sc[nd - 1]; }
+};
+
+int open_call(MriCall& c, MriOp op, const dinv_mri_desc* d, const float* in, const float* maps, const float* mask,
+              const float* out, void* workspace, size_t ws_bytes, dinv_stream_t stream) {
     if (int e = validate(d)) return e;
-    if (d->batch == 0) return 0;
-    DINV_REQUIRE(normal_ok(d), "dinv_mri_normal: unsupported sizes (see dinv_mri_normal_supported)");
-    DINV_REQUIRE(x && out && workspace, "null tensor pointer");
+    c.d = d;
+    c.empty = d->batch == 0;
+    if (c.empty) return 0;
+    if (op == kMriATA) DINV_REQUIRE(normal_ok(d), "dinv_mri_normal: unsupported sizes (see dinv_mri_normal_supported)");
+    DINV_REQUIRE(in && out && workspace, "null tensor pointer");
     DINV_REQUIRE(ws_bytes >= dinv_mri_workspace_bytes(d), "workspace too small: %zu < %zu", ws_bytes,
                  dinv_mri_workspace_bytes(d));
     DINV_REQUIRE((d->maps_batch != 0) == (maps != nullptr), "maps pointer / maps_batch mismatch");
     DINV_REQUIRE((d->mask_batch != 0) == (mask != nullptr), "mask pointer / mask_batch mismatch");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int nd = d->ndim;
-    const int64_t W = d->dims[nd - 1];
-    const int64_t vol = volume(d);
-    const int64_t R = vol / W;
-    float2* t = reinterpret_cast<float2*>(workspace);
-    const int64_t P = (int64_t)d->batch * d->coils;
-    const float2* mp = reinterpret_cast<const float2*>(maps);
-#ifndef DINV_NO_WAVE2D
-    if (mriw::wave2d_ok(d, 2)) return mriw::run_wave2d(d, 2, x, mp, mask, out, t, s);
-#endif
-    const float scw = 1.0f / sqrtf((float)W);
-    const int64_t N0 = d->dims[0], Q0 = vol / N0;
-    const float sc0 = 1.0f / sqrtf((float)N0);
-    // first pass (x, S -> t, transformed along the first axis) -> (cols(H)) -> rows(W): F, M^2, F^H in one tile ->
-    // (cols(H)^-1) -> cols(first axis)^-1 -> coil combination: the k-space tensor is never formed
-    int e = 0;
-    C2CIo fio{t, t, 0, 0};
-    if (Q0 % 4 == 0 && N0 > 16) {
-        switch (d->dims[0]) {
-#define DINV_CASE(NN) case NN: e = launch_cols_expand_fwd<NN>(x, mp, t, d->batch, d->coils, d->maps_batch, Q0, d->table[0], sc0, s); break;
-            DINV_CASE(32) DINV_STATIC_SIZES(DINV_CASE)
-#undef DINV_CASE
-        }
-    } else {
-        ColsCoilLoadIo cio{x, mp, t, d->coils, d->maps_batch, 0, 0};
-        e = launch_cols(cio, P, Q0, d->plan[0], d->table[0], 0, 1, sc0, s, d->coils);
+    c.pipeline = wave_ok(d, op) ? kWave : (all_static(d) ? kStatic : kGeneric);
+    c.s = reinterpret_cast<hipStream_t>(stream);
+    c.nd = d->ndim;
+    c.W = d->dims[c.nd - 1];
+    c.vol = volume(d);
+    c.R = c.vol / c.W;
+    c.P = (int64_t)d->batch * d->coils;
+    c.N0 = d->dims[0];
+    c.Q0 = c.vol / c.N0;
+    c.t = reinterpret_cast<float2*>(workspace);
+    c.maps = reinterpret_cast<const float2*>(maps);
+    c.mask = mask;
+    for (int i = 0; i < c.nd; ++i) c.sc[i] = 1.0f / sqrtf((float)d->dims[i]);
+    return 0;
+}
+
+// static pipeline, two rules that are NOT the same.  First pass of A / A^T A: the fused expansion loads 16 bytes per lane of
+// the rows behind a multi-stage first axis.  Last pass of A^T / A^T A: the streaming combination takes 4 pixels of the VOLUME.
+bool expand_fused(const MriCall& c) { return c.Q0 % 4 == 0 && c.N0 > 16; }
+bool combine_streamed(const MriCall& c) { return c.vol % 4 == 0 && c.N0 > 16; }
+
+// ---- the passes.  Each is one read and one write of t (or of x / y at the ends of a pipeline) and returns the status.
+int wave_pipeline(const MriCall& c, MriOp op, const float* in, float* out) {
+    return mriw::run_wave2d(c.d, op, in, c.maps, c.mask, out, c.t, c.s);
+}
+
+// static, first pass of A and A^T A: t[b, n] = F_axis0(S_n x_b)
+int expand_axis0(const MriCall& c, const float* x) {
+    const dinv_mri_desc* d = c.d;
+    if (!expand_fused(c)) {
+        // short first axis (a 3-D volume's depth): single-stage transform straight from x and the maps
+        ColsCoilLoadIo cio{x, c.maps, c.t, d->coils, d->maps_batch, 0, 0};
+        return launch_cols(cio, c.P, c.Q0, d->plan[0], d->table[0], 0, 1, c.sc[0], c.s, d->coils);
     }
-    if (e) return e;
-    if (nd == 3)
-        if ((e = launch_cols(fio, P * d->dims[0], W, d->plan[1], d->table[1], 0, 1, 1.0f / sqrtf((float)d->dims[1]), s))) return e;
-    switch ((int)W) {
-#define DINV_CASE(NN) case NN: e = launch_rows_normal<NN>(t, mask, P * R, R, d->coils, d->mask_batch, d->table[nd - 1], scw, s); break;
-        DINV_STATIC_SIZES(DINV_CASE)
+    // coil expansion + transform along the first axis, t written once
+    switch (d->dims[0]) {
+#define DINV_CASE(NN) case NN: return launch_cols_expand_fwd<NN>(x, c.maps, c.t, d->batch, d->coils, d->maps_batch, c.Q0, d->table[0], c.sc[0], c.s);
+        DINV_CASE(32) DINV_STATIC_SIZES(DINV_CASE)
 #undef DINV_CASE
-        default: return fail(2, "dinv_mri_normal: no static rows plan for %d", (int)W);
+        default: return fail(2, "no fused expand pass for length %d", d->dims[0]);   // (all_static admits no other length)
     }
-    if (e) return e;
-    if (nd == 3)
-        if ((e = launch_cols(fio, P * d->dims[0], W, d->plan[1], d->table[1], 1, 1, 1.0f / sqrtf((float)d->dims[1]), s))) return e;
-    if (vol % 4 == 0 && N0 > 16) {
-        if ((e = launch_cols(fio, P, Q0, d->plan[0], d->table[0], 1, 1, sc0, s))) return e;
-        const dim3 grid((unsigned)ceil_div(vol / 4, 256), (unsigned)ceil_div(d->batch, CB));
-        hipLaunchKernelGGL((mri_coil_combine_kernel<8>), grid, dim3(256), 0, s, t, mp, out, vol, d->batch, d->coils, d->maps_batch);
+}
+
+// every pipeline, 3-D only: the middle axis of t in place
+int mid_axis(const MriCall& c, int inverse) {
+    if (c.nd != 3) return 0;
+    C2CIo io{c.t, c.t, 0, 0};
+    return launch_cols(io, c.P * c.N0, c.W, c.d->plan[1], c.d->table[1], inverse, 1, c.sc[1], c.s);
+}
+
+// static, last pass of A^T and A^T A: x_b = sum_n conj(S_n) F^-1_axis0(t[b, n])
+int combine_axis0(const MriCall& c, float* x) {
+    const dinv_mri_desc* d = c.d;
+    if (combine_streamed(c)) {
+        // C2C pass along the first axis in place, then a wide streaming coil combination.  A fused form (one workgroup
+        // walking the coils of a column tile, next coil's loads in flight during the transform) was built in round 3 and
+        // measured 2x slower than these two passes (152 vs 44 + 27 us at cfg2): the serial coil loop leaves too few
+        // independent tiles in flight
+        C2CIo io{c.t, c.t, 0, 0};
+        if (int e = launch_cols(io, c.P, c.Q0, d->plan[0], d->table[0], 1, 1, c.sc[0], c.s)) return e;
+        const dim3 grid((unsigned)ceil_div(c.vol / 4, 256), (unsigned)ceil_div(d->batch, CB));
+        hipLaunchKernelGGL((mri_coil_combine_kernel<8>), grid, dim3(256), 0, c.s, c.t, c.maps, x, c.vol, d->batch, d->coils,
+                           d->maps_batch);
         DINV_CHECK_LAUNCH();
         return 0;
     }
-    return launch_cols_combine_inv<16>(t, mp, out, d->batch, d->coils, d->maps_batch, Q0, d->table[0], sc0, s);
+    // short first axis (a 3-D volume's depth): single-stage inverse transform with the coil sum in its store phase
+    return launch_cols_combine_inv<16>(c.t, c.maps, x, d->batch, d->coils, d->maps_batch, c.Q0, d->table[0], c.sc[0], c.s);
+}
+
+// static, the masked rows passes: t -> y * mask (A), y * mask -> t (A^T), t <- F^-1(M^2 F t) (A^T A)
+int rows_mask_store(const MriCall& c, float* y) {
+    RowsPlanarMaskStoreIo io{c.t, y, c.mask, c.d->coils, c.d->mask_batch, c.R, c.W, 0, 0};
+    return launch_rows(io, c.P * c.R, c.plan_w(), c.table_w(), 0, 1, c.sc_w(), c.s);
+}
+int rows_mask_load(const MriCall& c, const float* y) {
+    RowsPlanarMaskLoadIo io{y, c.mask, c.t, c.d->coils, c.d->mask_batch, c.R, c.W, 0, 0};
+    return launch_rows(io, c.P * c.R, c.plan_w(), c.table_w(), 1, 1, c.sc_w(), c.s);
+}
+int rows_normal(const MriCall& c) {
+    switch ((int)c.W) {
+#define DINV_CASE(NN) case NN: return launch_rows_normal<NN>(c.t, c.mask, c.P * c.R, c.R, c.d->coils, c.d->mask_batch, c.table_w(), c.sc_w(), c.s);
+        DINV_STATIC_SIZES(DINV_CASE)
+#undef DINV_CASE
+        default: return fail(2, "dinv_mri_normal: no static rows plan for %d", (int)c.W);
+    }
+}
+
+// generic, A: x, S -> t along the rows, then t -> y * mask along the first axis
+int rows_coil_load(const MriCall& c, const float* x) {
+    RowsCoilLoadIo io{x, c.maps, c.t, c.d->coils, c.d->maps_batch, c.R, c.W, 0, 0};
+    return launch_rows(io, c.P * c.R, c.plan_w(), c.table_w(), 0, 1, c.sc_w(), c.s);
+}
+int cols_mask_store(const MriCall& c, float* y) {
+    ColsPlanarMaskStoreIo io{c.t, y, c.mask, c.d->coils, c.d->mask_batch, 0, 0};
+    return launch_cols(io, c.P, c.Q0, c.d->plan[0], c.d->table[0], 0, 1, c.sc[0], c.s);
+}
+
+// generic, A^T: y * mask -> t along the first axis.  The rows pass behind it needs no more LDS than the forward's rows pass:
+// refuse here, before anything is written, where that one refuses too.  (launch_rows' own line-count check, blocks < 2^31, can
+// still refuse after this pass has written t; it needs more than 2^31 rows of one length, past any workspace this gets)
+int cols_mask_load(const MriCall& c, const float* y) {
+    const dinv_fft_plan& pw = c.plan_w();
+    DINV_REQUIRE(fft_lds_bytes(pw, rows_lines_per_block(pw)) <= kMaxLdsBytes, "fft length %d does not fit the 160 KiB LDS tile",
+                 pw.n);
+    ColsPlanarMaskLoadIo io{y, c.mask, c.t, c.d->coils, c.d->mask_batch, 0, 0};
+    return launch_cols(io, c.P, c.Q0, c.d->plan[0], c.d->table[0], 1, 1, c.sc[0], c.s);
+}
+
+// generic, last pass of A^T: x_b = sum_n conj(S_n) F^-1_W(t[b, n]), by the first of three routes that takes the row length
+int rows_combine(const MriCall& c, float* x) {
+    const dinv_mri_desc* d = c.d;
+    const dinv_fft_plan& pw = c.plan_w();
+    const int64_t nlines = (int64_t)d->batch * c.R;
+    // 1. a static plan: the coil sum in the registers of the last stage
+    switch (pw.n) {
+#define DINV_CASE(NN) case NN: return launch_combine_static<NN>(c.t, c.maps, x, nlines, c.R, d->coils, d->maps_batch, c.table_w(), c.sc_w(), c.s);
+        DINV_STATIC_SIZES(DINV_CASE)
+#undef DINV_CASE
+        default: break;
+    }
+    int lpb = rows_lines_per_block(pw);
+    if (lpb > 16) lpb = 16;
+    const int LS = fft_line_stride(pw.n);
+    const size_t lds = fft_lds_bytes(pw, lpb) + (size_t)lpb * LS * sizeof(float2);
+    if (lds <= kMaxLdsBytes) {
+        // 2. the combine tile (FFT tile + an lpb x LS accumulator) fits the LDS
+        if (lds > kDefaultLdsBytes) if (int e = raise_lds_cap<mri_rows_combine_kernel>(kMaxLdsBytes)) return e;
+        hipLaunchKernelGGL(mri_rows_combine_kernel, dim3((unsigned)ceil_div(nlines, lpb)), dim3(256), lds, c.s, c.t, c.maps, x, nlines, c.R,
+                           d->coils, d->maps_batch, lpb, pw, c.table_w(), 1, c.sc_w());
+        DINV_CHECK_LAUNCH();
+        return 0;
+    }
+    // 3. it does not: the in-place inverse rows pass, which has the forward's LDS limit, then a per-pixel coil combination
+    C2CIo io{c.t, c.t, 0, 0};
+    if (int e = launch_rows(io, c.P * c.R, pw, c.table_w(), 1, 1, c.sc_w(), c.s)) return e;
+    const int64_t total = (int64_t)d->batch * c.vol;
+    const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(total, 256), 4 * kMaxGrid);
+    hipLaunchKernelGGL(mri_coil_combine_any_kernel, dim3(grid), dim3(256), 0, c.s, c.t, c.maps, x, c.vol, total, d->coils,
+                       d->maps_batch);
+    DINV_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace
+
+// ---- the entry points: open the call, then the passes of its pipeline (the table at the top of the file)
+extern "C" size_t dinv_mri_workspace_bytes(const dinv_mri_desc* d) {
+    if (!d || d->ndim < 2 || d->ndim > 3) return 0;
+    return (size_t)d->batch * d->coils * volume(d) * sizeof(float2);
+}
+
+extern "C" int dinv_mri_forward(const dinv_mri_desc* d, const float* x, const float* maps, const float* mask,
+                                float* y, void* workspace, size_t ws_bytes, dinv_stream_t stream) {
+    MriCall c;
+    if (int e = open_call(c, kMriA, d, x, maps, mask, y, workspace, ws_bytes, stream)) return e;
+    if (c.empty) return 0;
+    if (c.pipeline == kWave) return wave_pipeline(c, kMriA, x, y);
+    if (c.pipeline == kStatic) {
+        if (int e = expand_axis0(c, x)) return e;
+        if (int e = mid_axis(c, 0)) return e;
+        return rows_mask_store(c, y);
+    }
+    if (int e = rows_coil_load(c, x)) return e;
+    if (int e = mid_axis(c, 0)) return e;
+    return cols_mask_store(c, y);
+}
+
+extern "C" int dinv_mri_adjoint(const dinv_mri_desc* d, const float* y, const float* maps, const float* mask,
+                                float* x, void* workspace, size_t ws_bytes, dinv_stream_t stream) {
+    MriCall c;
+    if (int e = open_call(c, kMriAT, d, y, maps, mask, x, workspace, ws_bytes, stream)) return e;
+    if (c.empty) return 0;
+    if (c.pipeline == kWave) return wave_pipeline(c, kMriAT, y, x);
+    if (c.pipeline == kStatic) {
+        if (int e = rows_mask_load(c, y)) return e;
+        if (int e = mid_axis(c, 1)) return e;
+        return combine_axis0(c, x);
+    }
+    if (int e = cols_mask_load(c, y)) return e;
+    if (int e = mid_axis(c, 1)) return e;
+    return rows_combine(c, x);
+}
+
+extern "C" int dinv_mri_normal_supported(const dinv_mri_desc* d) { return d && validate(d) == 0 && normal_ok(d) ? 1 : 0; }
+
+extern "C" int dinv_mri_normal(const dinv_mri_desc* d, const float* x, const float* maps, const float* mask, float* out,
+                               void* workspace, size_t ws_bytes, dinv_stream_t stream) {
+    MriCall c;
+    if (int e = open_call(c, kMriATA, d, x, maps, mask, out, workspace, ws_bytes, stream)) return e;
+    if (c.empty) return 0;
+    if (c.pipeline == kWave) return wave_pipeline(c, kMriATA, x, out);
+    // (normal_ok: the static pipeline; there is no generic one)
+    if (int e = expand_axis0(c, x)) return e;
+    if (int e = mid_axis(c, 0)) return e;
+    if (int e = rows_normal(c)) return e;
+    if (int e = mid_axis(c, 1)) return e;
+    return combine_axis0(c, out);
 }

@@ -27,9 +27,12 @@
 #endif
 
 namespace dinv {
+
+enum MriOp : int { kMriA = 0, kMriAT = 1, kMriATA = 2 };      // the operator of a call, here and in mri.hip
+
 namespace mriw {
 
-constexpr int CB = 64;      // rows of a column block (the 64-point transforms)
+constexpr int CB = 64;     // rows of a column block (the 64-point transforms)
 constexpr int CG = 32;      // columns of a column-pass tile (128 B of a planar row, 256 B of an interleaved one)
 
 __device__ __forceinline__ void unpack_c4(const float4& a, const float4& b, float2 (&v)[4]) {
@@ -556,15 +559,15 @@ __global__ __launch_bounds__(64 * WPB, DINV_MRIW_MINW) void rows_combine_kernel(
 }
 
 // ------------------------------------------------------------------ host side
-// op: 0 = A, 1 = A^T, 2 = A^T A.  The last passes of A^T / A^T A walk the coils inside one wave (B * R * W / 32 resp. B * 64 waves):
+// The last passes of A^T / A^T A walk the coils inside one wave (B * R * W / 32 resp. B * 64 waves):
 // below ~1000 of them the chip is not filled and the workgroup-cooperative pipelines of mri.hip are faster (measured at 4 slices
 // of 8 coils 320 x 320: 0.072 / 0.089 ms against 0.045 / 0.070 ms)
-inline bool wave2d_ok(const dinv_mri_desc* d, int op) {
+inline bool wave2d_ok(const dinv_mri_desc* d, MriOp op) {
     if (d->ndim != 2) return false;
     const int H = d->dims[0], W = d->dims[1];
     if (!(H == 256 || H == 320 || H == 512) || !(W == 256 || W == 320 || W == 512)) return false;
     const int64_t images = (int64_t)d->batch * d->coils;
-    if (op != 0 && (int64_t)d->batch * CB < 1024 && d->reserved != 1) return false;
+    if (op != kMriA && (int64_t)d->batch * CB < 1024 && d->reserved != 1) return false;
     return images * CB * (W / CG) * (H / CB) < (1ll << 31) && (int64_t)H * W < (1ll << 24);
 }
 
@@ -638,35 +641,31 @@ int launch_cols64(int W, float2* t, float* y, const float* mask, int64_t images,
     return 0;
 }
 
-// op: 0 = A (x -> y), 1 = A^T (y -> x), 2 = A^T A (x -> out)
-inline int run_wave2d(const dinv_mri_desc* d, int op, const float* in, const float2* maps, const float* mask, float* out, float2* t,
-                      hipStream_t s) {
-    const int H = d->dims[0], W = d->dims[1];
+// the pipeline of `op` at H = R * 64: in = x (A, A^T A) or y (A^T), out = y (A) or x
+template <int R>
+int run_wave2d_r(const dinv_mri_desc* d, MriOp op, const float* in, const float2* maps, const float* mask, float* out, float2* t,
+                 hipStream_t s) {
+    const int W = d->dims[1];
     const int64_t images = (int64_t)d->batch * d->coils;
     const void *th = d->table[0], *tw = d->table[1];
-    int e = 0;
-#define DINV_RUN(RR)                                                                                                              \
-    do {                                                                                                                          \
-        if (op == 0) {                                                                                                            \
-            if ((e = (launch_rows_dif<RR, false>(W, in, maps, nullptr, t, images, d->coils, d->maps_batch, tw, th, s)))) return e; \
-            return launch_cols64<RR, 0>(W, t, out, mask, images, d->coils, d->mask_batch, th, s);                                 \
-        } else if (op == 1) {                                                                                                     \
-            if ((e = (launch_rows_dif<RR, true>(W, in, nullptr, mask, t, images, d->coils, d->mask_batch, tw, th, s)))) return e;  \
-            return launch_cols64_combine<RR>(W, t, maps, out, d->batch, d->coils, d->maps_batch, th, s);                          \
-        } else {                                                                                                                  \
-            if ((e = (launch_rows_dif<RR, false>(W, in, maps, nullptr, t, images, d->coils, d->maps_batch, tw, th, s)))) return e; \
-            if ((e = launch_cols64<RR, 2>(W, t, nullptr, mask, images, d->coils, d->mask_batch, th, s))) return e;                \
-            return launch_rows_combine<RR>(W, t, maps, out, d->batch, d->coils, d->maps_batch, tw, th, s);                        \
-        }                                                                                                                         \
-    } while (0)
-    switch (H / CB) {
-        case 4: DINV_RUN(4); break;
-        case 5: DINV_RUN(5); break;
-        case 8: DINV_RUN(8); break;
-        default: break;
+    if (op == kMriAT) {
+        if (int e = launch_rows_dif<R, true>(W, in, nullptr, mask, t, images, d->coils, d->mask_batch, tw, th, s)) return e;
+        return launch_cols64_combine<R>(W, t, maps, out, d->batch, d->coils, d->maps_batch, th, s);
     }
-#undef DINV_RUN
-    return fail(2, "mri wave pipeline: unsupported height %d", H);
+    if (int e = launch_rows_dif<R, false>(W, in, maps, nullptr, t, images, d->coils, d->maps_batch, tw, th, s)) return e;
+    if (op == kMriA) return launch_cols64<R, 0>(W, t, out, mask, images, d->coils, d->mask_batch, th, s);
+    if (int e = launch_cols64<R, 2>(W, t, nullptr, mask, images, d->coils, d->mask_batch, th, s)) return e;
+    return launch_rows_combine<R>(W, t, maps, out, d->batch, d->coils, d->maps_batch, tw, th, s);
+}
+
+inline int run_wave2d(const dinv_mri_desc* d, MriOp op, const float* in, const float2* maps, const float* mask, float* out, float2* t,
+                      hipStream_t s) {
+    switch (d->dims[0] / CB) {
+        case 4: return run_wave2d_r<4>(d, op, in, maps, mask, out, t, s);
+        case 5: return run_wave2d_r<5>(d, op, in, maps, mask, out, t, s);
+        case 8: return run_wave2d_r<8>(d, op, in, maps, mask, out, t, s);
+        default: return fail(2, "mri wave pipeline: unsupported height %d", d->dims[0]);
+    }
 }
 
 }  // namespace mriw

@@ -61,10 +61,6 @@ def _declare(lib):
     lib.dinv_fft_table_bytes.argtypes = [i32]
     lib.dinv_fft_plan_init.argtypes = [i32, ctypes.POINTER(FftPlan), vp]
     lib.dinv_fft_c2c_axis.argtypes = [vp, vp, i64, i64, ctypes.POINTER(FftPlan), vp, i32, i32, f32, vp]
-    lib.dinv_mri_workspace_bytes.restype = sz
-    lib.dinv_mri_workspace_bytes.argtypes = [ctypes.POINTER(MriDesc)]
-    for name in ("dinv_mri_forward", "dinv_mri_adjoint"):
-        getattr(lib, name).argtypes = [ctypes.POINTER(MriDesc), vp, vp, vp, vp, vp, sz, vp]
     # the other symbol groups are declared by the modules that own them, each in its _declare(lib)
 
 

@@ -7,11 +7,10 @@ Replaces the ATen sequences of ``MultiCoilMRI.A`` (mri.py:254-272), ``MultiCoilM
 from __future__ import annotations
 
 import ctypes
-import os
 
 import torch
 
-from . import MriDesc, check, f32c, fft_plan, lib, ptr, require_hip, stream_ptr
+from . import MriDesc, check, declare_once, f32c, fft_plan, lib, ptr, require_hip, stream_ptr
 
 
 # Test hook (dinv_mri_desc.reserved = 1): take the wave-autonomous 2-D pipelines (csrc/mri_wave.hpp) whenever the sizes allow,
@@ -56,42 +55,44 @@ def _prep_maps(maps, vol, batch):
     return maps
 
 
-def _forward_raw(x, maps, mask, coil_dim):
-    dev = require_hip(x, maps, mask)
-    x = f32c(x)
-    if x.shape[1] != 2:
-        raise ValueError("x must be of shape (B,2,...,H,W)")
-    B, vol = x.shape[0], tuple(x.shape[2:])
+def _declare(l):
+    vp, sz, desc = ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(MriDesc)
+    l.dinv_mri_workspace_bytes.restype = sz
+    l.dinv_mri_workspace_bytes.argtypes = [desc]
+    l.dinv_mri_normal_supported.argtypes = [desc]
+    for name in ("dinv_mri_forward", "dinv_mri_adjoint", "dinv_mri_normal"):
+        getattr(l, name).argtypes = [desc, vp, vp, vp, vp, vp, sz, vp]
+
+
+def _l():
+    return declare_once(lib(), _declare)
+
+
+def _call(entry, inp, maps, mask, coil_dim):
+    """One call of the library.  entry = "forward" (A: x [B,2,vol] -> y [B,2,N,vol], or [B,2,vol] if not coil_dim), "adjoint"
+    (A^T: y -> x), "normal" (A^T A: x -> x, for the sizes the library supports) or "normal_supported" (x -> that answer)."""
+    dev = require_hip(inp, maps, mask)
+    inp = f32c(inp)
+    adjoint = entry == "adjoint"
+    if inp.shape[1] != 2:
+        raise ValueError("y must be of shape (B,2,N,...,H,W)" if adjoint else "x must be of shape (B,2,...,H,W)")
+    B = inp.shape[0]
+    vol = tuple(inp.shape[3:]) if adjoint and coil_dim else tuple(inp.shape[2:])
     maps = _prep_maps(maps, vol, B)
     mask = _prep_mask(mask, vol, B)
     N = 1 if maps is None else maps.shape[1]
+    if adjoint:
+        N = inp.shape[2] if coil_dim else 1
+        if maps is not None and maps.shape[1] != N:
+            raise ValueError(f"y has {N} coils but coil_maps has {maps.shape[1]}")
     d, keep = _desc(B, N, vol, mask, maps, coil_dim, dev)
-    yshape = (B, 2, N, *vol) if coil_dim else (B, 2, *vol)
-    y = torch.empty(yshape, device=dev, dtype=torch.float32)
-    ws = torch.empty(lib().dinv_mri_workspace_bytes(ctypes.byref(d)), device=dev, dtype=torch.uint8)
-    check(lib().dinv_mri_forward(ctypes.byref(d), ptr(x), ptr(None if maps is None else torch.view_as_real(maps)),
-                                 ptr(mask), ptr(y), ptr(ws), ws.numel(), stream_ptr(dev)))
-    return y
-
-
-def _adjoint_raw(y, maps, mask, coil_dim):
-    dev = require_hip(y, maps, mask)
-    y = f32c(y)
-    if y.shape[1] != 2:
-        raise ValueError("y must be of shape (B,2,N,...,H,W)")
-    B = y.shape[0]
-    vol = tuple(y.shape[3:]) if coil_dim else tuple(y.shape[2:])
-    maps = _prep_maps(maps, vol, B)
-    mask = _prep_mask(mask, vol, B)
-    N = y.shape[2] if coil_dim else 1
-    if maps is not None and maps.shape[1] != N:
-        raise ValueError(f"y has {N} coils but coil_maps has {maps.shape[1]}")
-    d, keep = _desc(B, N, vol, mask, maps, coil_dim, dev)
-    x = torch.empty((B, 2, *vol), device=dev, dtype=torch.float32)
-    ws = torch.empty(lib().dinv_mri_workspace_bytes(ctypes.byref(d)), device=dev, dtype=torch.uint8)
-    check(lib().dinv_mri_adjoint(ctypes.byref(d), ptr(y), ptr(None if maps is None else torch.view_as_real(maps)),
-                                 ptr(mask), ptr(x), ptr(ws), ws.numel(), stream_ptr(dev)))
-    return x
+    if entry == "normal_supported":
+        return bool(_l().dinv_mri_normal_supported(ctypes.byref(d)))
+    out = torch.empty((B, 2, N, *vol) if entry == "forward" and coil_dim else (B, 2, *vol), device=dev, dtype=torch.float32)
+    ws = torch.empty(_l().dinv_mri_workspace_bytes(ctypes.byref(d)), device=dev, dtype=torch.uint8)
+    check(getattr(_l(), "dinv_mri_" + entry)(ctypes.byref(d), ptr(inp), ptr(None if maps is None else torch.view_as_real(maps)),
+                                             ptr(mask), ptr(out), ptr(ws), ws.numel(), stream_ptr(dev)))
+    return out
 
 
 def _as_complex(t):   # [B,2,...] real pairs -> complex [B,...]
@@ -102,14 +103,14 @@ def _per_coil_adjoint(y, mask, coil_dim):
     """u_n = F^H(mask * y_n) for every coil, without the coil combination: the coils ride along the batch axis of the
     single-coil kernel.  y [B,2,N,vol] (or [B,2,vol]) -> complex [B,N,vol]."""
     if not coil_dim:
-        return _as_complex(_adjoint_raw(y, None, mask, False))[:, None]
+        return _as_complex(_call("adjoint", y, None, mask, False))[:, None]
     B, _, N = y.shape[:3]
     vol = tuple(y.shape[3:])
     yb = y.permute(0, 2, 1, *range(3, y.ndim)).reshape(B * N, 2, *vol)
     mb = mask
     if mask is not None and mask.shape[0] == B and B > 1:
         mb = mask.repeat_interleave(N, dim=0)
-    return _as_complex(_adjoint_raw(yb, None, mb, False)).reshape(B, N, *vol)
+    return _as_complex(_call("adjoint", yb, None, mb, False)).reshape(B, N, *vol)
 
 
 def _reduce_like(g, ref):
@@ -131,7 +132,7 @@ class _MriForward(torch.autograd.Function):
     # (forward / setup_context form: usable under torch.func transforms - the reference's adjoint_function is torch.func.vjp)
     @staticmethod
     def forward(x, maps, mask, coil_dim):
-        return _forward_raw(x, maps, mask, coil_dim)
+        return _call("forward", x, maps, mask, coil_dim)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -147,7 +148,7 @@ class _MriForward(torch.autograd.Function):
             u = _per_coil_adjoint(g, mask, ctx.coil_dim)
             gmaps = _reduce_like(u * _as_complex(x).conj()[:, None], maps).to(maps.dtype)
         if mask is not None and ctx.needs_input_grad[2]:
-            gmask = _mask_grad(g * _forward_raw(x, maps, None, ctx.coil_dim), mask, ctx.coil_dim)
+            gmask = _mask_grad(g * _call("forward", x, maps, None, ctx.coil_dim), mask, ctx.coil_dim)
         return gx, gmaps, gmask, None
 
 
@@ -156,7 +157,7 @@ class _MriAdjoint(torch.autograd.Function):
 
     @staticmethod
     def forward(y, maps, mask, coil_dim):
-        return _adjoint_raw(y, maps, mask, coil_dim)
+        return _call("adjoint", y, maps, mask, coil_dim)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -172,28 +173,8 @@ class _MriAdjoint(torch.autograd.Function):
             u = _per_coil_adjoint(y, mask, ctx.coil_dim)
             gmaps = _reduce_like(_as_complex(g).conj()[:, None] * u, maps).to(maps.dtype)
         if mask is not None and ctx.needs_input_grad[2]:
-            gmask = _mask_grad(_forward_raw(g, maps, None, ctx.coil_dim) * y, mask, ctx.coil_dim)
+            gmask = _mask_grad(_call("forward", g, maps, None, ctx.coil_dim) * y, mask, ctx.coil_dim)
         return gy, gmaps, gmask, None
-
-
-def _normal_raw(x, maps, mask, coil_dim):
-    """A^T A x through ``dinv_mri_normal`` (no k-space tensor); None when the sizes have no static plan."""
-    dev = require_hip(x, maps, mask)
-    x = f32c(x)
-    if x.shape[1] != 2:
-        raise ValueError("x must be of shape (B,2,...,H,W)")
-    B, vol = x.shape[0], tuple(x.shape[2:])
-    maps = _prep_maps(maps, vol, B)
-    mask = _prep_mask(mask, vol, B)
-    N = 1 if maps is None else maps.shape[1]
-    d, keep = _desc(B, N, vol, mask, maps, coil_dim, dev)
-    if not lib().dinv_mri_normal_supported(ctypes.byref(d)):
-        return None
-    out = torch.empty_like(x)
-    ws = torch.empty(lib().dinv_mri_workspace_bytes(ctypes.byref(d)), device=dev, dtype=torch.uint8)
-    check(lib().dinv_mri_normal(ctypes.byref(d), ptr(x), ptr(None if maps is None else torch.view_as_real(maps)),
-                                ptr(mask), ptr(out), ptr(ws), ws.numel(), stream_ptr(dev)))
-    return out
 
 
 class _MriNormal(torch.autograd.Function):
@@ -201,7 +182,7 @@ class _MriNormal(torch.autograd.Function):
 
     @staticmethod
     def forward(x, maps, mask, coil_dim):
-        return _normal_raw(x, maps, mask, coil_dim)
+        return _call("normal", x, maps, mask, coil_dim)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -218,18 +199,13 @@ ENABLE_FUSED_NORMAL = True    # test hook: False evaluates A^T A as adjoint(forw
 
 
 def mri_normal(x, coil_maps=None, mask=None, coil_dim=True):
-    """``A^T A x = sum_n conj(S_n) F^H(mask^2 F(S_n x))`` in one kernel chain that never writes k-space.  Falls back to
-    adjoint(forward(x)) for sizes without a static FFT plan, or when the mask / coil maps themselves need gradients."""
+    """``A^T A x = sum_n conj(S_n) F^H(mask^2 F(S_n x))`` in one kernel chain that never writes k-space, for the sizes
+    ``dinv_mri_normal_supported`` admits.  adjoint(forward(x)) for the others, or when the mask / coil maps themselves need
+    gradients."""
     needs_param_grad = torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in (coil_maps, mask))
-    if not needs_param_grad and ENABLE_FUSED_NORMAL:
-        B, vol = x.shape[0], tuple(x.shape[2:])
-        if all(_static_ok(n) for n in vol) and vol[-1] >= 64 and vol[0] >= 16:
-            return _MriNormal.apply(x, coil_maps, mask, bool(coil_dim))
+    if not needs_param_grad and ENABLE_FUSED_NORMAL and _call("normal_supported", x, coil_maps, mask, bool(coil_dim)):
+        return _MriNormal.apply(x, coil_maps, mask, bool(coil_dim))
     return mri_adjoint(mri_forward(x, coil_maps, mask, coil_dim), coil_maps, mask, coil_dim)
-
-
-def _static_ok(n: int) -> bool:   # sizes with a compile-time plan (csrc/fft_static.hpp: has_static_plan)
-    return n in (16, 32, 64, 128, 256, 320, 512)
 
 
 def mri_forward(x, coil_maps=None, mask=None, coil_dim=True):

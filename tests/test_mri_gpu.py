@@ -245,8 +245,9 @@ def test_single_coil_normal_operator_and_autograd(dev):
 def runner(dev):
     import mri_cases as K
     from deepinv_amd import hip
+    from deepinv_amd.hip import mri as M
 
-    return K.Runner(hip.lib(), dev, lambda: hip.stream_ptr(dev), lambda n: hip.fft_plan(n, dev))
+    return K.Runner(M._l(), dev, lambda: hip.stream_ptr(dev), lambda n: hip.fft_plan(n, dev))     # (with the MRI prototypes)
 
 
 def _table():
