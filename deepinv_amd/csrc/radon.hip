@@ -15,9 +15,9 @@
 // materialised: coordinates are recomputed from cos/sin/linspace tables.  Images (forward) and sinograms
 // (adjoint) are first re-packed batch-innermost ([..][NB]) so one bilinear tap of NB images is a single
 // 4*NB-byte vector load and the coordinate/weight arithmetic is amortised over the NB images.
-#include "common.hpp"
+#include "radon_common.hpp"
 
-#pragma clang fp contract(off)  // forward and adjoint must round the sample coordinates identically
+#pragma clang fp contract(off)  // forward and adjoint must round the sample coordinates identically (radon_common.hpp)
 
 using namespace dinv;
 
@@ -27,44 +27,6 @@ struct RadonGeom {
     int32_t n_img, W, G, pad, A, circle, NB, groups;
     float scale;  // 1/operator_norm (tomography.py:253-254)
 };
-
-// the disc mask of radon.py:270-283, xa^2 + ya^2 <= 1, with both squares rounded before the sum as the reference's tensor
-// expression rounds them: the squares are made opaque so that the compiler cannot contract the sum into a fused multiply-add,
-// which moves points that lie on the circle outside it (row 56, column 7 of a 71 x 71 disc: 0.6^2 + 0.8^2 rounds to 1 in fp32,
-// fma(0.6, 0.6, 0.8^2) to 1 + 2^-23)
-__device__ __forceinline__ bool in_unit_disc(float xa, float ya) {
-    float x2 = xa * xa, y2 = ya * ya;
-#ifndef DINV_EMU
-    asm volatile("" : "+v"(x2), "+v"(y2));
-#endif
-    return x2 + y2 <= 1.0f;
-}
-
-// sample position (ix -> column, iy -> row) for grid = [gx, gy] R^T (radon.py:334-341), unnormalised as ATen's grid_sampler
-// (align_corners=True): the fan-beam kernels, whose lattice is not uniform
-__device__ __forceinline__ void sample_pos(float c, float s, float xj, float xi, float gm1, float& ix, float& iy) {
-    const float gx = fmaf(c, xj, s * xi);
-    const float gy = fmaf(-s, xj, c * xi);
-    ix = ((gx + 1.0f) * 0.5f) * gm1;
-    iy = ((gy + 1.0f) * 0.5f) * gm1;
-}
-
-// Parallel beam: the lattice is the rotation of the UNIFORM base grid xn = linspace(-1, 1, G) of affine_grid (radon.py:252-342), so
-// in pixel units the sample of ray j at step i is   (ix, iy) = ctr + R (j - ctr, i - ctr),   ctr = (G - 1) / 2:
-//   ix = fma(s, i - ctr, fma(c, j - ctr, ctr)),   iy = fma(c, i - ctr, fma(-s, j - ctr, ctr))
-// - one fused multiply-add per coordinate and step from a per-ray base (j - ctr and i - ctr are exact), two roundings of at most
-// half an ulp of G each (6e-5 pixel at G = 729), against nine operations per step for the chain above, whose own roundings are of
-// the same size.  Bit-identical in the forward and adjoint kernels of radon.hip and radon_tiled.hip: the adjoint's tap weights
-// are the forward's.  (The base grid is the reference's linspace by construction; the `xn` arguments of the entry points keep
-// their place in the ABI, the parallel-beam kernels do not read them.)
-__device__ __forceinline__ void ray_base(float c, float s, float dj, float ctr, float& bx, float& by) {
-    bx = fmaf(c, dj, ctr);
-    by = fmaf(-s, dj, ctr);
-}
-__device__ __forceinline__ void lattice_pos(float c, float s, float bx, float by, float di, float& ix, float& iy) {
-    ix = fmaf(s, di, bx);
-    iy = fmaf(c, di, by);
-}
 
 // ---- x [n_img, W, W] -> xp [groups][(G+2)][(G+2)][NB], zero ring + zero padding, optional circle mask
 template <int NB>
@@ -77,12 +39,7 @@ __global__ void radon_pack_image(RadonGeom g, const float* __restrict__ x, float
         const int r = rem / GP - 1 - g.pad, c = rem % GP - 1 - g.pad;  // original image coordinates
         float v[NB];
         bool in = r >= 0 && r < g.W && c >= 0 && c < g.W;
-        if (in && g.circle) {
-            // radon.py:270-283: mask = (xax^2 + yax^2 <= 1), axes = 2*k/(W-1) - 1
-            const float ya = 2.0f * (float)c / (float)(g.W - 1) - 1.0f;
-            const float xa = 2.0f * (float)r / (float)(g.W - 1) - 1.0f;
-            in = in_unit_disc(xa, ya);
-        }
+        if (in && g.circle) in = pixel_in_disc(r, c, g.W);
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
             const int n = grp * NB + k;
@@ -120,16 +77,7 @@ __global__ __launch_bounds__(256) void radon_fwd_kernel(RadonGeom g, const float
         int x0 = (int)fx, y0 = (int)fy;
         const bool ok = x0 >= -1 && x0 <= g.G - 1 && y0 >= -1 && y0 <= g.G - 1;
         if (!ok) continue;
-        const float w00 = (1.0f - tx) * (1.0f - ty), w01 = tx * (1.0f - ty);
-        const float w10 = (1.0f - tx) * ty, w11 = tx * ty;
-        const float* p = img + ((int64_t)(y0 + 1) * GP + (x0 + 1)) * NB;
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            acc[k] = fmaf(w00, p[k], acc[k]);
-            acc[k] = fmaf(w01, p[NB + k], acc[k]);
-            acc[k] = fmaf(w10, p[(int64_t)GP * NB + k], acc[k]);
-            acc[k] = fmaf(w11, p[(int64_t)GP * NB + NB + k], acc[k]);
-        }
+        add_taps<NB>(acc, img + ((int64_t)(y0 + 1) * GP + (x0 + 1)) * NB, GP, tx, ty);
     }
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
@@ -138,20 +86,10 @@ __global__ __launch_bounds__(256) void radon_fwd_kernel(RadonGeom g, const float
     }
 }
 
-// ---- sino [n_img, G, A] -> sp [groups][A][G][NB]
+// ---- sino [n_img, N, A] -> sp [groups][A][N][NB]  (N = G; the detector count for the fan beam)
 template <int NB>
-__global__ void radon_pack_sino(RadonGeom g, const float* __restrict__ sino, float* __restrict__ sp) {
-    const int64_t total = (int64_t)g.groups * g.A * g.G;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-        const int grp = (int)(idx / ((int64_t)g.A * g.G));
-        const int rem = (int)(idx - (int64_t)grp * g.A * g.G);
-        const int a = rem / g.G, j = rem - a * g.G;
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            const int n = grp * NB + k;
-            sp[idx * NB + k] = n < g.n_img ? sino[((int64_t)n * g.G + j) * g.A + a] : 0.f;
-        }
-    }
+__global__ void radon_pack_sino(int n_img, int groups, int A, int N, const float* __restrict__ sino, float* __restrict__ sp) {
+    pack_sino<NB>(n_img, groups, A, N, 0, sino, sp);
 }
 
 // ---- exact adjoint as a gather: one thread = one image pixel of NB images, loop over angles
@@ -174,12 +112,7 @@ __global__ __launch_bounds__(256) void radon_adj_kernel(RadonGeom g, const float
     float acc[NB];
 #pragma unroll
     for (int k = 0; k < NB; ++k) acc[k] = 0.f;
-    bool live = true;
-    if (g.circle) {
-        const float ya = 2.0f * (float)col / (float)(g.W - 1) - 1.0f;
-        const float xa = 2.0f * (float)row / (float)(g.W - 1) - 1.0f;
-        live = in_unit_disc(xa, ya);
-    }
+    const bool live = !g.circle || pixel_in_disc(row, col, g.W);
     if (live) {
         for (int a = 0; a < g.A; ++a) {
             const float c = cs_s[a].x, s = cs_s[a].y;
@@ -263,16 +196,7 @@ __global__ __launch_bounds__(256) void radon_fan_fwd_kernel(RadonGeom g, int n_d
         if (!(fx >= -1.0f && fx <= (float)(g.G - 1) && fy >= -1.0f && fy <= (float)(g.G - 1))) continue;
         const float tx = ix - fx, ty = iy - fy;
         const int x0 = (int)fx, y0 = (int)fy;
-        const float w00 = (1.0f - tx) * (1.0f - ty), w01 = tx * (1.0f - ty);
-        const float w10 = (1.0f - tx) * ty, w11 = tx * ty;
-        const float* p = img + ((int64_t)(y0 + 1) * GP + (x0 + 1)) * NB;
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            acc[k] = fmaf(w00, p[k], acc[k]);
-            acc[k] = fmaf(w01, p[NB + k], acc[k]);
-            acc[k] = fmaf(w10, p[(int64_t)GP * NB + k], acc[k]);
-            acc[k] = fmaf(w11, p[(int64_t)GP * NB + NB + k], acc[k]);
-        }
+        add_taps<NB>(acc, img + ((int64_t)(y0 + 1) * GP + (x0 + 1)) * NB, GP, tx, ty);
     }
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
@@ -316,12 +240,7 @@ __global__ __launch_bounds__(256) void radon_fan_adj_kernel(RadonGeom g, int n_d
     float acc[NB];
 #pragma unroll
     for (int k = 0; k < NB; ++k) acc[k] = 0.f;
-    bool live = true;
-    if (g.circle) {
-        const float ya = 2.0f * (float)col / (float)(g.W - 1) - 1.0f;
-        const float xa = 2.0f * (float)row / (float)(g.W - 1) - 1.0f;
-        live = in_unit_disc(xa, ya);
-    }
+    const bool live = !g.circle || pixel_in_disc(row, col, g.W);
     if (live) {
         for (int a = 0; a < g.A; ++a) {
             const float c = cs[a].x, s = cs[a].y;
@@ -446,16 +365,15 @@ __global__ __launch_bounds__(256) void ramp_kernel(int n_img, int N, int A, cons
         if (j0 + q < N) out[((int64_t)n * N + j0 + q) * A + a] = acc[q];
 }
 
-int check_desc(const dinv_radon_desc* d, RadonGeom* g) {
-    DINV_REQUIRE(d != nullptr, "null descriptor");
-    DINV_REQUIRE(d->n_img >= 0 && d->width >= 2 && d->grid >= d->width && d->n_angles >= 1, "bad radon geometry");
-    DINV_REQUIRE(d->pad_before >= 0 && d->pad_before + d->width <= d->grid, "bad padding");
-    g->n_img = d->n_img; g->W = d->width; g->G = d->grid; g->pad = d->pad_before; g->A = d->n_angles;
-    g->circle = d->circle; g->scale = d->scale;
-    g->NB = d->n_img >= 8 ? 8 : d->n_img >= 4 ? 4 : d->n_img >= 2 ? 2 : 1;
-    g->groups = d->n_img == 0 ? 0 : (d->n_img + g->NB - 1) / g->NB;
+int check_desc(const dinv_radon_desc* d, RadonGeom* g) { return desc_to_geom(d, g, &g->NB); }
+
+int check_fan_desc(const dinv_radon_desc* d, int32_t n_det, RadonGeom* g) {
+    if (int e = check_desc(d, g)) return e;
+    DINV_REQUIRE(n_det >= 1, "bad detector count %d", n_det);
     return 0;
 }
+
+int64_t packed_image_cells(const RadonGeom& g) { return (int64_t)g.groups * (g.G + 2) * (g.G + 2); }
 
 }  // namespace
 
@@ -463,59 +381,40 @@ extern "C" size_t dinv_radon_workspace_bytes(const dinv_radon_desc* d, int32_t a
     RadonGeom g;
     if (!d || check_desc(d, &g)) return 0;
     if (adjoint) return (size_t)g.groups * g.A * g.G * g.NB * sizeof(float);
-    return (size_t)g.groups * (g.G + 2) * (g.G + 2) * g.NB * sizeof(float);
+    return (size_t)packed_image_cells(g) * g.NB * sizeof(float);
 }
-
-#define DINV_NB_DISPATCH(NBV, STMT)                                  \
-    switch (NBV) {                                                   \
-        case 8: { constexpr int NB = 8; STMT; } break;               \
-        case 4: { constexpr int NB = 4; STMT; } break;               \
-        case 2: { constexpr int NB = 2; STMT; } break;               \
-        default: { constexpr int NB = 1; STMT; } break;              \
-    }
 
 extern "C" int dinv_radon_forward(const dinv_radon_desc* d, const float* x, const float* xn, const float* cs,
                                   float* sino, void* ws, size_t ws_bytes, dinv_stream_t stream) {
     RadonGeom g;
-    if (int e = check_desc(d, &g)) return e;
-    if (g.n_img == 0) return 0;
-    DINV_REQUIRE(x && xn && cs && sino && ws, "null pointer");
-    DINV_REQUIRE(ws_bytes >= dinv_radon_workspace_bytes(d, 0), "workspace too small");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* xp = reinterpret_cast<float*>(ws);
-    const float2* cs2 = reinterpret_cast<const float2*>(cs);
-    const int64_t npk = (int64_t)g.groups * (g.G + 2) * (g.G + 2);
-    const unsigned pk_blocks = (unsigned)std::min<int64_t>(ceil_div(npk, 256), 65535);
-    const dim3 grid((g.G + 63) / 64, (g.A + 3) / 4, g.groups);
-    DINV_NB_DISPATCH(g.NB, {
-        hipLaunchKernelGGL(radon_pack_image<NB>, dim3(pk_blocks), dim3(256), 0, s, g, x, xp);
-        hipLaunchKernelGGL(radon_fwd_kernel<NB>, grid, dim3(256), g.G * sizeof(float), s, g, xp, xn, cs2, sino);
+    return radon_call(check_desc(d, &g), g, x && xn && cs && sino && ws, ws_bytes, dinv_radon_workspace_bytes(d, 0), cs, ws, stream,
+                      [&](hipStream_t s, const float2* cs2, float* xp) {
+        const dim3 grid((g.G + 63) / 64, (g.A + 3) / 4, g.groups);
+        return dispatch_nb(g.NB, [&](auto nb) {
+            constexpr int NB = decltype(nb)::value;
+            hipLaunchKernelGGL(radon_pack_image<NB>, pack_blocks(packed_image_cells(g)), dim3(256), 0, s, g, x, xp);
+            hipLaunchKernelGGL(radon_fwd_kernel<NB>, grid, dim3(256), g.G * sizeof(float), s, g, xp, xn, cs2, sino);
+            return 0;
+        });
     });
-    DINV_CHECK_LAUNCH();
-    return 0;
 }
 
 extern "C" int dinv_radon_adjoint(const dinv_radon_desc* d, const float* sino, const float* xn, const float* cs,
                                   float* x, void* ws, size_t ws_bytes, dinv_stream_t stream) {
     RadonGeom g;
-    if (int e = check_desc(d, &g)) return e;
-    if (g.n_img == 0) return 0;
-    DINV_REQUIRE(x && xn && cs && sino && ws, "null pointer");
-    DINV_REQUIRE(ws_bytes >= dinv_radon_workspace_bytes(d, 1), "workspace too small");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* sp = reinterpret_cast<float*>(ws);
-    const float2* cs2 = reinterpret_cast<const float2*>(cs);
-    const int64_t npk = (int64_t)g.groups * g.A * g.G;
-    const unsigned pk_blocks = (unsigned)std::min<int64_t>(ceil_div(npk, 256), 65535);
-    const dim3 grid((g.W + 63) / 64, (g.W + 3) / 4, g.groups);
-    const size_t lds = (size_t)(((g.G + 1) / 2) * 2) * sizeof(float) + (size_t)g.A * sizeof(float2);
-    DINV_REQUIRE(lds <= 64 * 1024, "too many angles/detectors for the LDS tables (%zu B)", lds);
-    DINV_NB_DISPATCH(g.NB, {
-        hipLaunchKernelGGL(radon_pack_sino<NB>, dim3(pk_blocks), dim3(256), 0, s, g, sino, sp);
-        hipLaunchKernelGGL(radon_adj_kernel<NB>, grid, dim3(256), lds, s, g, sp, xn, cs2, x);
+    return radon_call(check_desc(d, &g), g, x && xn && cs && sino && ws, ws_bytes, dinv_radon_workspace_bytes(d, 1), cs, ws, stream,
+                      [&](hipStream_t s, const float2* cs2, float* sp) {
+        const dim3 grid((g.W + 63) / 64, (g.W + 3) / 4, g.groups);
+        const size_t lds = (size_t)(((g.G + 1) / 2) * 2) * sizeof(float) + (size_t)g.A * sizeof(float2);
+        DINV_REQUIRE(lds <= 64 * 1024, "too many angles/detectors for the LDS tables (%zu B)", lds);
+        return dispatch_nb(g.NB, [&](auto nb) {
+            constexpr int NB = decltype(nb)::value;
+            hipLaunchKernelGGL(radon_pack_sino<NB>, pack_blocks((int64_t)g.groups * g.A * g.G), dim3(256), 0, s, g.n_img, g.groups,
+                               g.A, g.G, sino, sp);
+            hipLaunchKernelGGL(radon_adj_kernel<NB>, grid, dim3(256), lds, s, g, sp, xn, cs2, x);
+            return 0;
+        });
     });
-    DINV_CHECK_LAUNCH();
-    return 0;
 }
 
 extern "C" int dinv_radon_backproject(const dinv_radon_desc* d, const float* sino, const float* xn, const float* cs,
@@ -546,60 +445,49 @@ extern "C" int dinv_radon_ramp(int32_t n_img, int32_t n_det, int32_t n_angles, c
     return 0;
 }
 
+
 extern "C" size_t dinv_radon_fan_workspace_bytes(const dinv_radon_desc* d, int32_t n_det, int32_t adjoint) {
     RadonGeom g;
     if (!d || n_det < 1 || check_desc(d, &g)) return 0;
     if (adjoint) return (size_t)g.groups * g.A * n_det * g.NB * sizeof(float);
-    return (size_t)g.groups * (g.G + 2) * (g.G + 2) * g.NB * sizeof(float);
+    return (size_t)packed_image_cells(g) * g.NB * sizeof(float);
 }
 
 extern "C" int dinv_radon_fan_forward(const dinv_radon_desc* d, int32_t n_det, const float* x, const float* xm,
                                       const float* sc, const float* yd, const float* cs, float* sino, void* ws,
                                       size_t ws_bytes, dinv_stream_t stream) {
     RadonGeom g;
-    if (int e = check_desc(d, &g)) return e;
-    DINV_REQUIRE(n_det >= 1, "bad detector count %d", n_det);
-    if (g.n_img == 0) return 0;
-    DINV_REQUIRE(x && xm && sc && yd && cs && sino && ws, "null pointer");
-    DINV_REQUIRE(ws_bytes >= dinv_radon_fan_workspace_bytes(d, n_det, 0), "workspace too small");
-    DINV_REQUIRE((size_t)2 * g.G * sizeof(float) <= 64 * 1024, "grid too large for the LDS tables");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* xp = reinterpret_cast<float*>(ws);
-    const float2* cs2 = reinterpret_cast<const float2*>(cs);
-    const int64_t npk = (int64_t)g.groups * (g.G + 2) * (g.G + 2);
-    const unsigned pk_blocks = (unsigned)std::min<int64_t>(ceil_div(npk, 256), 65535);
-    const dim3 grid((n_det + 63) / 64, (g.A + 3) / 4, g.groups);
-    DINV_NB_DISPATCH(g.NB, {
-        hipLaunchKernelGGL(radon_pack_image<NB>, dim3(pk_blocks), dim3(256), 0, s, g, x, xp);
-        hipLaunchKernelGGL(radon_fan_fwd_kernel<NB>, grid, dim3(256), 2 * g.G * sizeof(float), s, g, n_det, xp, xm, sc, yd, cs2, sino);
+    return radon_call(check_fan_desc(d, n_det, &g), g, x && xm && sc && yd && cs && sino && ws, ws_bytes,
+                      dinv_radon_fan_workspace_bytes(d, n_det, 0), cs, ws, stream,
+                      [&](hipStream_t s, const float2* cs2, float* xp) {
+        const size_t lds = (size_t)2 * g.G * sizeof(float);
+        DINV_REQUIRE(lds <= 64 * 1024, "grid too large for the LDS tables");
+        const dim3 grid((n_det + 63) / 64, (g.A + 3) / 4, g.groups);
+        return dispatch_nb(g.NB, [&](auto nb) {
+            constexpr int NB = decltype(nb)::value;
+            hipLaunchKernelGGL(radon_pack_image<NB>, pack_blocks(packed_image_cells(g)), dim3(256), 0, s, g, x, xp);
+            hipLaunchKernelGGL(radon_fan_fwd_kernel<NB>, grid, dim3(256), lds, s, g, n_det, xp, xm, sc, yd, cs2, sino);
+            return 0;
+        });
     });
-    DINV_CHECK_LAUNCH();
-    return 0;
 }
 
 extern "C" int dinv_radon_fan_adjoint(const dinv_radon_desc* d, int32_t n_det, const float* sino, const float* xm,
                                       const float* sc, const float* yd, const float* cs, float* x, void* ws,
                                       size_t ws_bytes, dinv_stream_t stream) {
     RadonGeom g;
-    if (int e = check_desc(d, &g)) return e;
-    DINV_REQUIRE(n_det >= 1, "bad detector count %d", n_det);
-    if (g.n_img == 0) return 0;
-    DINV_REQUIRE(x && xm && sc && yd && cs && sino && ws, "null pointer");
-    DINV_REQUIRE(ws_bytes >= dinv_radon_fan_workspace_bytes(d, n_det, 1), "workspace too small");
-    const size_t lds = (size_t)(3 * g.G + n_det) * sizeof(float);
-    DINV_REQUIRE(lds <= 64 * 1024, "grid / detector too large for the LDS tables (%zu B)", lds);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    float* sp = reinterpret_cast<float*>(ws);
-    const float2* cs2 = reinterpret_cast<const float2*>(cs);
-    RadonGeom gs = g;
-    gs.G = n_det;   // radon_pack_sino: [n_img, n_det, A] -> [groups][A][n_det][NB]
-    const int64_t npk = (int64_t)g.groups * g.A * n_det;
-    const unsigned pk_blocks = (unsigned)std::min<int64_t>(ceil_div(npk, 256), 65535);
-    const dim3 grid((g.W + 63) / 64, (g.W + 3) / 4, g.groups);
-    DINV_NB_DISPATCH(g.NB, {
-        hipLaunchKernelGGL(radon_pack_sino<NB>, dim3(pk_blocks), dim3(256), 0, s, gs, sino, sp);
-        hipLaunchKernelGGL(radon_fan_adj_kernel<NB>, grid, dim3(256), lds, s, g, n_det, sp, xm, sc, yd, cs2, x);
+    return radon_call(check_fan_desc(d, n_det, &g), g, x && xm && sc && yd && cs && sino && ws, ws_bytes,
+                      dinv_radon_fan_workspace_bytes(d, n_det, 1), cs, ws, stream,
+                      [&](hipStream_t s, const float2* cs2, float* sp) {
+        const size_t lds = (size_t)(3 * g.G + n_det) * sizeof(float);
+        DINV_REQUIRE(lds <= 64 * 1024, "grid / detector too large for the LDS tables (%zu B)", lds);
+        const dim3 grid((g.W + 63) / 64, (g.W + 3) / 4, g.groups);
+        return dispatch_nb(g.NB, [&](auto nb) {
+            constexpr int NB = decltype(nb)::value;
+            hipLaunchKernelGGL(radon_pack_sino<NB>, pack_blocks((int64_t)g.groups * g.A * n_det), dim3(256), 0, s, g.n_img, g.groups,
+                               g.A, n_det, sino, sp);
+            hipLaunchKernelGGL(radon_fan_adj_kernel<NB>, grid, dim3(256), lds, s, g, n_det, sp, xm, sc, yd, cs2, x);
+            return 0;
+        });
     });
-    DINV_CHECK_LAUNCH();
-    return 0;
 }

@@ -24,11 +24,12 @@
 //            digit-reversed output feeds the inverse decimation-in-time stages directly - no permutation pass.
 #include "common.hpp"
 #include "fft_core.hpp"
+#include "radon_common.hpp"
 
 #include <cmath>
 #include <vector>
 
-#pragma clang fp contract(off)  // forward and adjoint must round the sample coordinates identically (and like radon.hip)
+#pragma clang fp contract(off)  // forward and adjoint must round the sample coordinates identically (radon_common.hpp)
 
 using namespace dinv;
 
@@ -64,37 +65,6 @@ struct TiledGeom {
     float scale;
 };
 
-// the disc mask of radon.py:270-283, xa^2 + ya^2 <= 1, with both squares rounded before the sum as the reference's tensor
-// expression rounds them: the squares are made opaque so that the compiler cannot contract the sum into a fused multiply-add,
-// which moves points that lie on the circle outside it (row 56, column 7 of a 71 x 71 disc: 0.6^2 + 0.8^2 rounds to 1 in fp32,
-// fma(0.6, 0.6, 0.8^2) to 1 + 2^-23)
-__device__ __forceinline__ bool in_unit_disc(float xa, float ya) {
-    float x2 = xa * xa, y2 = ya * ya;
-#ifndef DINV_EMU
-    asm volatile("" : "+v"(x2), "+v"(y2));
-#endif
-    return x2 + y2 <= 1.0f;
-}
-
-// identical to radon.hip (see the note there): sample position (ix -> column, iy -> row) of lattice point (j, i) of the rotated
-// uniform grid, (ix, iy) = ctr + R (j - ctr, i - ctr): a per-ray base and one fused multiply-add per coordinate and step
-__device__ __forceinline__ void ray_base(float c, float s, float dj, float ctr, float& bx, float& by) {
-    bx = fmaf(c, dj, ctr);
-    by = fmaf(-s, dj, ctr);
-}
-__device__ __forceinline__ void lattice_pos(float c, float s, float bx, float by, float di, float& ix, float& iy) {
-    ix = fmaf(s, di, bx);
-    iy = fmaf(c, di, by);
-}
-
-// bilinear weight of integer pixel p for a sample at position t along one axis.  With f = floor(t): p == f gives
-// 1 - (t - f) and p == f + 1 gives t - f, both EXACTLY what grid_sample's weights are (t - p is exact by Sterbenz,
-// and 1 - (1 - frac) is exact because frac is a multiple of ulp(t) >= 2^-23); any other p clamps to 0.
-__device__ __forceinline__ float weight_of(float t, float p) {
-    const float w = 1.0f - fabsf(t - p);
-    return w > 0.f ? w : 0.f;
-}
-
 template <int NB> struct Vec { static constexpr int V = NB >= 4 ? 4 : NB; static constexpr int PLANES = NB / V; };
 
 // ---------------------------------------------------------------------------------------------------- pack
@@ -112,11 +82,7 @@ __global__ void radon_pack_image2(TiledGeom g, const float* __restrict__ x, floa
         const int r = pr - 1 - g.pad, c = pc - 1 - g.pad;   // original image coordinates (row, col)
         bool in = r >= 0 && r < g.W && c >= 0 && c < g.W;
         bool in_t = in;
-        if (in && g.circle) {   // radon.py:270-283 (symmetric in r and c)
-            const float ya = 2.0f * (float)c / (float)(g.W - 1) - 1.0f;
-            const float xa = 2.0f * (float)r / (float)(g.W - 1) - 1.0f;
-            in = in_t = in_unit_disc(xa, ya);
-        }
+        if (in && g.circle) in = in_t = pixel_in_disc(r, c, g.W);   // (symmetric in r and c)
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
             const int n = grp * NB + k;
@@ -327,18 +293,7 @@ __global__ __launch_bounds__(512, MAXPF <= 10 ? 4 : 2) void radon_fwd_tiled_kern
 // sino [n_img, G, A] -> sp [groups][A][JPAD + G + JPAD][NB] (zero padded rows)
 template <int NB>
 __global__ void radon_pack_sino2(TiledGeom g, const float* __restrict__ sino, float* __restrict__ sp) {
-    const int GJ = g.G + 2 * JPAD;
-    const int64_t total = (int64_t)g.groups * g.A * GJ;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-        const int grp = (int)(idx / ((int64_t)g.A * GJ));
-        const int rem = (int)(idx - (int64_t)grp * g.A * GJ);
-        const int a = rem / GJ, j = rem - a * GJ - JPAD;
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            const int n = grp * NB + k;
-            sp[idx * NB + k] = (n < g.n_img && j >= 0 && j < g.G) ? sino[((int64_t)n * g.G + j) * g.A + a] : 0.f;
-        }
-    }
+    pack_sino<NB>(g.n_img, g.groups, g.A, g.G, JPAD, sino, sp);
 }
 
 template <int NB>
@@ -365,11 +320,7 @@ __global__ __launch_bounds__(256) void radon_adj_tiled_kernel(TiledGeom g, const
     const float dxc = (float)(blockIdx.x * 16 + g.pad) + 7.5f - ctr;   // tile centre
     const float dyc = (float)(blockIdx.y * 16 + g.pad) + 7.5f - ctr;
     bool live = col < g.W && row < g.W;
-    if (live && g.circle) {
-        const float ya = 2.0f * (float)col / (float)(g.W - 1) - 1.0f;
-        const float xa = 2.0f * (float)row / (float)(g.W - 1) - 1.0f;
-        live = in_unit_disc(xa, ya);
-    }
+    if (live && g.circle) live = pixel_in_disc(row, col, g.W);
     float acc[NB];
 #pragma unroll
     for (int k = 0; k < NB; ++k) acc[k] = 0.f;
@@ -581,15 +532,8 @@ __global__ __launch_bounds__(256) void ramp_fft_kernel(int n_img, int N, int A, 
 
 // ---------------------------------------------------------------------------------------------------- host side
 int make_geom(const dinv_radon_desc* d, TiledGeom* g, int* NBsel) {
-    DINV_REQUIRE(d != nullptr, "null descriptor");
-    DINV_REQUIRE(d->n_img >= 0 && d->width >= 2 && d->grid >= d->width && d->n_angles >= 1, "bad radon geometry");
-    DINV_REQUIRE(d->pad_before >= 0 && d->pad_before + d->width <= d->grid, "bad padding");
+    if (int e = desc_to_geom(d, g, NBsel)) return e;
     DINV_REQUIRE(d->grid <= MAXG, "detector count %d above the tiled kernels' limit %d", d->grid, MAXG);
-    g->n_img = d->n_img; g->W = d->width; g->G = d->grid; g->pad = d->pad_before; g->A = d->n_angles;
-    g->circle = d->circle; g->scale = d->scale;
-    int NB = d->n_img >= 8 ? 8 : d->n_img >= 4 ? 4 : d->n_img >= 2 ? 2 : 1;
-    *NBsel = NB;
-    g->groups = d->n_img == 0 ? 0 : (d->n_img + NB - 1) / NB;
     g->njb = (d->grid + 63) / 64;
     g->nbands = (d->grid + 1 + BH - 1) / BH;
     g->PH = g->nbands * BH + 1;
@@ -613,14 +557,6 @@ PlanLayout plan_layout(int A, int njb, int nbands, int kw) {
     return L;
 }
 constexpr int kSlackFloats = 4096;   // tail of the packed image: windows may run past the end of the last row
-
-#define DINV_NB_DISPATCH(NBV, STMT)                                  \
-    switch (NBV) {                                                   \
-        case 8: { constexpr int NB = 8; STMT; } break;               \
-        case 4: { constexpr int NB = 4; STMT; } break;               \
-        case 2: { constexpr int NB = 2; STMT; } break;               \
-        default: { constexpr int NB = 1; STMT; } break;              \
-    }
 
 }  // namespace
 
@@ -780,37 +716,29 @@ extern "C" int dinv_radon_forward_tiled(const dinv_radon_desc* d, const dinv_rad
                                         float* sino, void* ws, size_t ws_bytes, dinv_stream_t stream) {
     TiledGeom g;
     int NBsel;
-    if (int e = make_geom(d, &g, &NBsel)) return e;
-    if (g.n_img == 0) return 0;
-    DINV_REQUIRE(plan && plan_dev && x && xn && cs && sino && ws, "null pointer");
-    DINV_REQUIRE(plan->grid == g.G && plan->n_angles == g.A && plan->n_jblocks == g.njb && plan->n_bands == g.nbands,
-                 "plan does not match the descriptor");
-    DINV_REQUIRE(ws_bytes >= dinv_radon_tiled_workspace_bytes(d, 0), "workspace too small");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int kw = plan->kw;
-    DINV_REQUIRE(kw == 1 || kw == 2 || kw == 4 || kw == 8, "bad plan (kw = %d)", kw);
-    const PlanLayout L = plan_layout(g.A, g.njb, g.nbands, kw);
-    const int32_t* blob = reinterpret_cast<const int32_t*>(plan_dev);
-    const float2* cs2 = reinterpret_cast<const float2*>(cs);
-    const int64_t npk = (int64_t)g.groups * g.PH * g.PW;
-    const unsigned pk_blocks = (unsigned)std::min<int64_t>(ceil_div(npk, 256), 65535);
-    g.WW = plan->win_w;
-    {
+    return radon_call(make_geom(d, &g, &NBsel), g, plan && plan_dev && x && xn && cs && sino && ws, ws_bytes,
+                      dinv_radon_tiled_workspace_bytes(d, 0), cs, ws, stream, [&](hipStream_t s, const float2* cs2, float* xp) {
+        DINV_REQUIRE(plan->grid == g.G && plan->n_angles == g.A && plan->n_jblocks == g.njb && plan->n_bands == g.nbands,
+                     "plan does not match the descriptor");
+        const int kw = plan->kw;
+        DINV_REQUIRE(kw == 1 || kw == 2 || kw == 4 || kw == 8, "bad plan (kw = %d)", kw);
+        const PlanLayout L = plan_layout(g.A, g.njb, g.nbands, kw);
+        const int32_t* blob = reinterpret_cast<const int32_t*>(plan_dev);
+        g.WW = plan->win_w;
         const uint64_t rowlen = (uint64_t)g.WW * (NBsel >= 8 ? 2 : 1);
         g.row_magic = (uint32_t)((((uint64_t)1 << 32) + rowlen - 1) / rowlen);
-    }
-    DINV_REQUIRE(g.groups <= 65535 && plan->n_chunks_plain <= 65535 && plan->n_chunks_swap <= 65535, "grid too large");
-    DINV_NB_DISPATCH(NBsel, {
-        float* xp = reinterpret_cast<float*>(ws);
-        float* xpt = xp + (size_t)g.groups * g.PH * g.PW * NB;
-        const size_t lds = ((size_t)((g.G + 3) & ~3) + (size_t)(BH + 1) * g.WW * NB) * sizeof(float);
-        DINV_REQUIRE(lds <= kMaxLdsBytes && (size_t)g.WW * NB <= kSlackFloats,
-                     "window of %d columns x %d images does not fit the LDS: use dinv_radon_forward", g.WW, NB);
-        hipLaunchKernelGGL(radon_pack_image2<NB>, dim3(pk_blocks), dim3(256), 0, s, g, x, xp, xpt);
-        if (kw == 8) DINV_FWD_LAUNCH(9); else DINV_FWD_LAUNCH(18);
+        DINV_REQUIRE(g.groups <= 65535 && plan->n_chunks_plain <= 65535 && plan->n_chunks_swap <= 65535, "grid too large");
+        return dispatch_nb(NBsel, [&](auto nb) {
+            constexpr int NB = decltype(nb)::value;
+            float* xpt = xp + (size_t)g.groups * g.PH * g.PW * NB;
+            const size_t lds = ((size_t)((g.G + 3) & ~3) + (size_t)(BH + 1) * g.WW * NB) * sizeof(float);
+            DINV_REQUIRE(lds <= kMaxLdsBytes && (size_t)g.WW * NB <= kSlackFloats,
+                         "window of %d columns x %d images does not fit the LDS: use dinv_radon_forward", g.WW, NB);
+            hipLaunchKernelGGL(radon_pack_image2<NB>, pack_blocks((int64_t)g.groups * g.PH * g.PW), dim3(256), 0, s, g, x, xp, xpt);
+            if (kw == 8) DINV_FWD_LAUNCH(9); else DINV_FWD_LAUNCH(18);
+            return 0;
+        });
     });
-    DINV_CHECK_LAUNCH();
-    return 0;
 }
 
 #endif  // DINV_RADON_PART != 2
@@ -821,28 +749,22 @@ extern "C" int dinv_radon_adjoint_tiled(const dinv_radon_desc* d, const float* s
                                         dinv_stream_t stream) {
     TiledGeom g;
     int NBsel;
-    if (int e = make_geom(d, &g, &NBsel)) return e;
-    if (g.n_img == 0) return 0;
-    DINV_REQUIRE(x && xn && cs && sino && ws, "null pointer");
-    DINV_REQUIRE(ws_bytes >= dinv_radon_tiled_workspace_bytes(d, 1), "workspace too small");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const float2* cs2 = reinterpret_cast<const float2*>(cs);
-    const int64_t npk = (int64_t)g.groups * g.A * (g.G + 2 * JPAD);
-    const unsigned pk_blocks = (unsigned)std::min<int64_t>(ceil_div(npk, 256), 65535);
-    DINV_REQUIRE(g.groups <= 65535, "too many images per call");
-    DINV_NB_DISPATCH(NBsel, {
-        float* sp = reinterpret_cast<float*>(ws);
-        const size_t lds = ((size_t)((g.G + 3) & ~3) + (size_t)KA * JW * NB) * sizeof(float) + KA * sizeof(float2) +
-                           KA * sizeof(int);
-        DINV_REQUIRE(lds <= kMaxLdsBytes, "grid of %d does not fit the LDS tile of the tiled adjoint", g.G);
-        if (lds > kDefaultLdsBytes)
-            if (int e = raise_lds_cap<radon_adj_tiled_kernel<NB>>(kMaxLdsBytes)) return e;
-        hipLaunchKernelGGL(radon_pack_sino2<NB>, dim3(pk_blocks), dim3(256), 0, s, g, sino, sp);
-        hipLaunchKernelGGL(radon_adj_tiled_kernel<NB>, dim3((g.W + 15) / 16, (g.W + 15) / 16, g.groups), dim3(256), lds, s,
-                           g, (const float*)sp, xn, cs2, norm_dev, x);
+    return radon_call(make_geom(d, &g, &NBsel), g, x && xn && cs && sino && ws, ws_bytes, dinv_radon_tiled_workspace_bytes(d, 1),
+                      cs, ws, stream, [&](hipStream_t s, const float2* cs2, float* sp) {
+        DINV_REQUIRE(g.groups <= 65535, "too many images per call");
+        return dispatch_nb(NBsel, [&](auto nb) {
+            constexpr int NB = decltype(nb)::value;
+            const size_t lds = ((size_t)((g.G + 3) & ~3) + (size_t)KA * JW * NB) * sizeof(float) + KA * sizeof(float2) +
+                               KA * sizeof(int);
+            DINV_REQUIRE(lds <= kMaxLdsBytes, "grid of %d does not fit the LDS tile of the tiled adjoint", g.G);
+            if (lds > kDefaultLdsBytes)
+                if (int e = raise_lds_cap<radon_adj_tiled_kernel<NB>>(kMaxLdsBytes)) return e;
+            hipLaunchKernelGGL(radon_pack_sino2<NB>, pack_blocks((int64_t)g.groups * g.A * (g.G + 2 * JPAD)), dim3(256), 0, s, g, sino, sp);
+            hipLaunchKernelGGL(radon_adj_tiled_kernel<NB>, dim3((g.W + 15) / 16, (g.W + 15) / 16, g.groups), dim3(256), lds, s,
+                               g, (const float*)sp, xn, cs2, norm_dev, x);
+            return 0;
+        });
     });
-    DINV_CHECK_LAUNCH();
-    return 0;
 }
 
 // ---- ramp filter: P, the Fourier filter of the reference and its digit-reversed device table

@@ -1,12 +1,15 @@
 """ctypes + autograd wrappers for the Radon kernels (csrc/radon_tiled.hip, csrc/radon.hip).
 
 Default path: the LDS-tiled forward / adjoint kernels and the FFT ramp filter; the operator norm of a normalised
-``Tomography`` is handed to the kernels as a DEVICE scalar (no host read-back per call).  ``DINV_RADON_TILED=0``
-selects the round-1 gather kernels (kept for detector counts above the tiled kernels' limit and as a cross-check)."""
+``Tomography`` is handed to the kernels as a DEVICE scalar (no host read-back per call).  The round-1 gather kernels serve
+detector counts above the tiled kernels' limit, angle lists that give the tiled forward fewer than 4 angles per workgroup, and
+the fan-beam geometry.  Every operator is one side of a pair (``ExactPair``, ``InterpolatingPair``, ``FanPair``) applied by
+one autograd function whose backward is the other side."""
 from __future__ import annotations
 
 import ctypes
-import os
+from dataclasses import dataclass
+from typing import Optional
 
 import torch
 
@@ -65,15 +68,16 @@ FORCE_TILED = False        # True: the LDS-tiled forward even for angle lists wi
 ENABLE_RAMP_FFT = True     # False: the direct-convolution ramp filter
 
 
-def _use_tiled(grid: int) -> bool:
-    return grid <= TILED_MAX_GRID and ENABLE_TILED
-
-
 class RadonGeometry:
     """Host-side tables built exactly like the reference builds its grids (radon.py:70-71, 242-250, 334-341), plus the
     window plan of the tiled forward kernel (angle chunks, per-band LDS windows; ``dinv_radon_plan_init``)."""
 
     def __init__(self, angles_deg: torch.Tensor, width: int, circle: bool, device):
+        self._build_tables(angles_deg, width, circle, device)
+        if self.device.type == "cuda" and self.G <= TILED_MAX_GRID:
+            self.build_plan()
+
+    def _build_tables(self, angles_deg, width, circle, device):
         sqrt2 = (2 * torch.ones(1)).sqrt()
         self.W = int(width)
         if circle:
@@ -86,20 +90,22 @@ class RadonGeometry:
         a = angles_deg.detach().to("cpu", torch.float32)
         theta = a * 4 * torch.ones(1).atan() / 180           # deg2rad (radon.py:70-71)
         self.A = int(a.numel())
-        cs_host = torch.stack([theta.cos(), theta.sin()], dim=1).contiguous()
-        self.cs = cs_host.to(device)
+        self.cs_host = torch.stack([theta.cos(), theta.sin()], dim=1).contiguous()
+        self.cs = self.cs_host.to(device)
         self.xn = torch.linspace(-1, 1, self.G).to(device)   # affine_grid base grid, align_corners=True
         # IRadon grid x-coordinate of angle column a (radon.py:474-489) -> unnormalised like grid_sample does
         X = torch.arange(self.A, dtype=torch.float32) * 2.0 / (self.A - 1) - 1.0 if self.A > 1 else torch.zeros(1)
         self.ixtab = (((X + 1.0) / 2) * (self.A - 1)).contiguous().to(device)
         self.device = torch.device(device)
         self.plan = self.plan_dev = None
-        if self.device.type == "cuda" and self.G <= TILED_MAX_GRID:
-            d = self.desc(1, 1.0)
-            blob = torch.zeros(_l().dinv_radon_plan_bytes(ctypes.byref(d)) // 4, dtype=torch.int32)
-            self.plan = RadonPlan()
-            check(_l().dinv_radon_plan_init(ctypes.byref(d), ptr(cs_host), ctypes.byref(self.plan), ptr(blob)))
-            self.plan_dev = blob[: self.plan.blob_words].to(device)
+
+    def build_plan(self):
+        """the window plan of the tiled forward (host side: dinv_radon_plan_init) and its device copy"""
+        d = self.desc(1, 1.0)
+        blob = torch.zeros(_l().dinv_radon_plan_bytes(ctypes.byref(d)) // 4, dtype=torch.int32)
+        self.plan = RadonPlan()
+        check(_l().dinv_radon_plan_init(ctypes.byref(d), ptr(self.cs_host), ctypes.byref(self.plan), ptr(blob)))
+        self.plan_dev = blob[: self.plan.blob_words].to(self.device)
 
     def desc(self, n_img: int, scale: float) -> RadonDesc:
         return RadonDesc(n_img, self.W, self.G, self.pad_before, self.A, int(self.circle), float(scale), 0)
@@ -113,76 +119,50 @@ def _norm_ptr(norm, dev):
     return ptr(norm)
 
 
-def _fwd(x, geo: RadonGeometry, norm, scale=1.0):
-    """x [B,C,W,W] -> [B,C,G,A] / norm * scale"""
-    dev = require_hip(x, geo.xn)
-    x = f32c(x)
-    B, C, H, W = x.shape
-    sino = torch.empty((B, C, geo.G, geo.A), device=dev, dtype=torch.float32)
+def _check_sinogram(y, n_det, what, n_angles):
+    if y.shape[-2] != n_det or y.shape[-1] != n_angles:
+        raise ValueError(f"sinogram of shape {tuple(y.shape)} does not match the operator ({n_det} {what}, {n_angles} angles)")
+
+
+def _chunks(n, step=65535):
+    """(start, end) of the pieces of n images a kernel with one image per grid-z block takes in one launch"""
+    for s in range(0, n, step):
+        yield s, min(n, s + step)
+
+
+def _launch(entry, ws_bytes, out, *head):
+    """entry(*head, out, a workspace of ws_bytes, its size, the stream) -> out"""
+    dev = out.device
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    check(entry(*head, ptr(out), ptr(ws), ws_bytes, stream_ptr(dev)))
+    return out
+
+
+def _div_norm(out, norm):
+    """the gather kernels take a host scalar only: the device norm divides on the device, after them"""
+    return out if norm is None else out.div_(norm)
+
+
+def _parallel(t, geo: RadonGeometry, norm, scale, adjoint):
+    """x [B,C,W,W] -> sinogram [B,C,G,A] (adjoint: the exact transpose), / norm * scale"""
+    dev = require_hip(t, geo.xn)
+    t = f32c(t)
+    B, C, H, W = t.shape
+    if adjoint:
+        _check_sinogram(t, geo.G, "detectors", geo.A)
+    out = torch.empty((B, C, geo.W, geo.W) if adjoint else (B, C, geo.G, geo.A), device=dev, dtype=torch.float32)
+    l, d = _l(), ctypes.byref(geo.desc(B * C, scale))
+    tables = (ptr(t), ptr(geo.xn), ptr(geo.cs))
     # few angles per workgroup (coarse or irregular angle lists) leave the LDS-tiled forward kernel under-occupied:
     # below 4 the gather kernel is the faster one (measured at 512^2: 60 angles, kw = 2)
-    if _use_tiled(geo.G) and geo.plan is not None and (geo.plan.kw >= 4 or FORCE_TILED):
-        d = geo.desc(B * C, scale)
-        ws = torch.empty(_l().dinv_radon_tiled_workspace_bytes(ctypes.byref(d), 0), device=dev, dtype=torch.uint8)
-        check(_l().dinv_radon_forward_tiled(ctypes.byref(d), ctypes.byref(geo.plan), ptr(geo.plan_dev), ptr(x), ptr(geo.xn),
-                                            ptr(geo.cs), _norm_ptr(norm, dev), ptr(sino), ptr(ws), ws.numel(),
-                                            stream_ptr(dev)))
-        return sino
-    d = geo.desc(B * C, scale)
-    ws = torch.empty(_l().dinv_radon_workspace_bytes(ctypes.byref(d), 0), device=dev, dtype=torch.uint8)
-    check(_l().dinv_radon_forward(ctypes.byref(d), ptr(x), ptr(geo.xn), ptr(geo.cs), ptr(sino), ptr(ws), ws.numel(),
-                                  stream_ptr(dev)))
-    return sino if norm is None else sino.div_(norm)   # the gather kernels take a host scalar only: divide on the device
-
-
-def _adj(y, geo: RadonGeometry, norm, scale=1.0):
-    dev = require_hip(y, geo.xn)
-    y = f32c(y)
-    B, C, G, A = y.shape
-    if G != geo.G or A != geo.A:
-        raise ValueError(f"sinogram of shape {tuple(y.shape)} does not match the operator ({geo.G} detectors, {geo.A} angles)")
-    x = torch.empty((B, C, geo.W, geo.W), device=dev, dtype=torch.float32)
-    if _use_tiled(geo.G):
-        d = geo.desc(B * C, scale)
-        ws = torch.empty(_l().dinv_radon_tiled_workspace_bytes(ctypes.byref(d), 1), device=dev, dtype=torch.uint8)
-        check(_l().dinv_radon_adjoint_tiled(ctypes.byref(d), ptr(y), ptr(geo.xn), ptr(geo.cs), _norm_ptr(norm, dev), ptr(x),
-                                            ptr(ws), ws.numel(), stream_ptr(dev)))
-        return x
+    if geo.G <= TILED_MAX_GRID and ENABLE_TILED and (adjoint or (geo.plan is not None and (geo.plan.kw >= 4 or FORCE_TILED))):
+        entry, plan = (l.dinv_radon_adjoint_tiled, ()) if adjoint else \
+            (l.dinv_radon_forward_tiled, (ctypes.byref(geo.plan), ptr(geo.plan_dev)))
+        return _launch(entry, l.dinv_radon_tiled_workspace_bytes(d, adjoint), out, d, *plan, *tables, _norm_ptr(norm, dev))
     # the gather adjoint keeps (cos, sin) of every angle in LDS behind G words: 4 * (G rounded up to even) + 8 * A <= 64 KiB, so
     # above TILED_MAX_GRID it raises (no fallback) for more than 6143 angles at G = 4097, fewer at larger G
-    d = geo.desc(B * C, scale)
-    ws = torch.empty(_l().dinv_radon_workspace_bytes(ctypes.byref(d), 1), device=dev, dtype=torch.uint8)
-    check(_l().dinv_radon_adjoint(ctypes.byref(d), ptr(y), ptr(geo.xn), ptr(geo.cs), ptr(x), ptr(ws), ws.numel(),
-                                  stream_ptr(dev)))
-    return x if norm is None else x.div_(norm)
-
-
-class _RadonFwd(torch.autograd.Function):
-    @staticmethod
-    def forward(x, geo, norm):
-        return _fwd(x, geo, norm)
-
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        _, ctx.geo, ctx.norm = inputs
-
-    @staticmethod
-    def backward(ctx, g):
-        return _RadonAdj.apply(g, ctx.geo, ctx.norm), None, None
-
-
-class _RadonAdj(torch.autograd.Function):
-    @staticmethod
-    def forward(y, geo, norm):
-        return _adj(y, geo, norm)
-
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        _, ctx.geo, ctx.norm = inputs
-
-    @staticmethod
-    def backward(ctx, g):
-        return _RadonFwd.apply(g, ctx.geo, ctx.norm), None, None
+    entry = l.dinv_radon_adjoint if adjoint else l.dinv_radon_forward
+    return _div_norm(_launch(entry, l.dinv_radon_workspace_bytes(d, adjoint), out, d, *tables), norm)
 
 
 def iradon_backproject(y, geo: RadonGeometry, scale=1.0):
@@ -190,46 +170,14 @@ def iradon_backproject(y, geo: RadonGeometry, scale=1.0):
     dev = require_hip(y, geo.xn)
     y = f32c(y)
     B, C, G, A = y.shape
-    if G != geo.G or A != geo.A:
-        raise ValueError(f"sinogram of shape {tuple(y.shape)} does not match the operator ({geo.G} detectors, {geo.A} angles)")
+    _check_sinogram(y, geo.G, "detectors", geo.A)
     out = torch.empty((B, C, geo.W, geo.W), device=dev, dtype=torch.float32)
     n = B * C
-    for s0 in range(0, n, 65535):
-        e = min(n, s0 + 65535)
-        d = geo.desc(e - s0, scale)
-        check(_l().dinv_radon_backproject(ctypes.byref(d), ptr(y.view(n, G, A)[s0:e]), ptr(geo.xn), ptr(geo.cs),
-                                          ptr(geo.ixtab), ptr(out.view(n, geo.W, geo.W)[s0:e]), stream_ptr(dev)))
+    for s, e in _chunks(n):
+        d = geo.desc(e - s, scale)
+        check(_l().dinv_radon_backproject(ctypes.byref(d), ptr(y.view(n, G, A)[s:e]), ptr(geo.xn), ptr(geo.cs),
+                                          ptr(geo.ixtab), ptr(out.view(n, geo.W, geo.W)[s:e]), stream_ptr(dev)))
     return out
-
-
-class _ApplyRadon(torch.autograd.Function):
-    """Radon / interpolating back-projection pair of the reference's ``ApplyRadon`` (radon.py:493-531): each one's
-    autograd backward is the other (an *inexact* adjoint pair by design)."""
-
-    @staticmethod
-    def forward(x, geo, scale, adjoint):
-        return iradon_backproject(x, geo, scale) if adjoint else _fwd(x, geo, None, scale)
-
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        _, ctx.geo, ctx.scale, ctx.adjoint = inputs
-
-    @staticmethod
-    def backward(ctx, g):
-        return _ApplyRadon.apply(g, ctx.geo, ctx.scale, not ctx.adjoint), None, None, None
-
-
-def apply_radon(x, geo, scale, adjoint):
-    return _ApplyRadon.apply(x, geo, float(scale), bool(adjoint))
-
-
-def radon_forward(x, geo, norm=None):
-    """Radon transform divided by the device scalar `norm` (None: unnormalised)"""
-    return _RadonFwd.apply(x, geo, norm)
-
-
-def radon_adjoint(y, geo, norm=None):
-    return _RadonAdj.apply(y, geo, norm)
 
 
 # --------------------------------------------------------------------------- fan-beam geometry
@@ -260,75 +208,102 @@ class FanGeometry(RadonGeometry):
     """RadonGeometry (padding, angle table) plus the fan-beam lattice tables; no tiled plan (gather kernels)."""
 
     def __init__(self, angles_deg, width, circle, device, fan_parameters=None):
-        super().__init__(angles_deg, width, circle, "cpu")      # host part only: no window plan for this geometry
+        self._build_tables(angles_deg, width, circle, device)
         self.fan_parameters, xm, sc, yd = fan_tables(self.G, self.W, fan_parameters)
         self.n_det = int(yd.numel())
-        self.device = torch.device(device)
-        self.cs, self.xn = self.cs.to(device), self.xn.to(device)
         self.xm, self.sc, self.yd = xm.to(device), sc.to(device), yd.to(device)
 
 
-def _fan_fwd(x, geo: FanGeometry, norm):
-    dev = require_hip(x, geo.xm)
-    x = f32c(x)
-    B, C = x.shape[:2]
-    sino = torch.empty((B, C, geo.n_det, geo.A), device=dev, dtype=torch.float32)
-    d = geo.desc(B * C, 1.0)
-    ws = torch.empty(_l().dinv_radon_fan_workspace_bytes(ctypes.byref(d), geo.n_det, 0), device=dev, dtype=torch.uint8)
-    check(_l().dinv_radon_fan_forward(ctypes.byref(d), geo.n_det, ptr(x), ptr(geo.xm), ptr(geo.sc), ptr(geo.yd), ptr(geo.cs),
-                                      ptr(sino), ptr(ws), ws.numel(), stream_ptr(dev)))
-    return sino if norm is None else sino.div_(norm)
+def _fan(t, geo: FanGeometry, norm, adjoint):
+    """x [B,C,W,W] -> sinogram [B,C,n_det,A] (adjoint: the exact transpose), / norm"""
+    dev = require_hip(t, geo.xm)
+    t = f32c(t)
+    B, C, N, A = t.shape
+    if adjoint:
+        _check_sinogram(t, geo.n_det, "detector pixels", geo.A)
+    out = torch.empty((B, C, geo.W, geo.W) if adjoint else (B, C, geo.n_det, geo.A), device=dev, dtype=torch.float32)
+    d = ctypes.byref(geo.desc(B * C, 1.0))
+    entry = _l().dinv_radon_fan_adjoint if adjoint else _l().dinv_radon_fan_forward
+    return _div_norm(_launch(entry, _l().dinv_radon_fan_workspace_bytes(d, geo.n_det, int(adjoint)), out, d, geo.n_det, ptr(t),
+                             ptr(geo.xm), ptr(geo.sc), ptr(geo.yd), ptr(geo.cs)), norm)
 
 
-def _fan_adj(y, geo: FanGeometry, norm):
-    dev = require_hip(y, geo.xm)
-    y = f32c(y)
-    B, C, N, A = y.shape
-    if N != geo.n_det or A != geo.A:
-        raise ValueError(f"sinogram of shape {tuple(y.shape)} does not match the operator ({geo.n_det} detector pixels, "
-                         f"{geo.A} angles)")
-    x = torch.empty((B, C, geo.W, geo.W), device=dev, dtype=torch.float32)
-    d = geo.desc(B * C, 1.0)
-    ws = torch.empty(_l().dinv_radon_fan_workspace_bytes(ctypes.byref(d), geo.n_det, 1), device=dev, dtype=torch.uint8)
-    check(_l().dinv_radon_fan_adjoint(ctypes.byref(d), geo.n_det, ptr(y), ptr(geo.xm), ptr(geo.sc), ptr(geo.yd), ptr(geo.cs),
-                                      ptr(x), ptr(ws), ws.numel(), stream_ptr(dev)))
-    return x if norm is None else x.div_(norm)
+# --------------------------------------------------------------------------- the operator pairs and their autograd
+@dataclass(frozen=True, eq=False)
+class ExactPair:
+    """parallel-beam Radon transform and its exact adjoint, divided by the device scalar `norm` (None: unnormalised)"""
+    geo: RadonGeometry
+    norm: Optional[torch.Tensor]
+
+    def fwd(self, t):
+        return _parallel(t, self.geo, self.norm, 1.0, False)
+
+    def adj(self, t):
+        return _parallel(t, self.geo, self.norm, 1.0, True)
 
 
-class _FanFwd(torch.autograd.Function):
+@dataclass(frozen=True, eq=False)
+class InterpolatingPair:
+    """Radon / interpolating back-projection pair of the reference's ``ApplyRadon`` (radon.py:493-531), times the host
+    scalar `scale`: each one's autograd backward is the other (an *inexact* adjoint pair by design)"""
+    geo: RadonGeometry
+    scale: float
+
+    def fwd(self, t):
+        return _parallel(t, self.geo, None, self.scale, False)
+
+    def adj(self, t):
+        return iradon_backproject(t, self.geo, self.scale)
+
+
+@dataclass(frozen=True, eq=False)
+class FanPair:
+    """fan-beam transform and its exact adjoint, divided by the device scalar `norm`"""
+    geo: FanGeometry
+    norm: Optional[torch.Tensor]
+
+    def fwd(self, t):
+        return _fan(t, self.geo, self.norm, False)
+
+    def adj(self, t):
+        return _fan(t, self.geo, self.norm, True)
+
+
+class _Apply(torch.autograd.Function):
+    """one side of an operator pair; its backward is the other side"""
+
     @staticmethod
-    def forward(x, geo, norm):
-        return _fan_fwd(x, geo, norm)
+    def forward(t, op, adjoint):
+        return op.adj(t) if adjoint else op.fwd(t)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        _, ctx.geo, ctx.norm = inputs
+        _, ctx.op, ctx.adjoint = inputs
 
     @staticmethod
     def backward(ctx, g):
-        return _FanAdj.apply(g, ctx.geo, ctx.norm), None, None
+        return _Apply.apply(g, ctx.op, not ctx.adjoint), None, None
 
 
-class _FanAdj(torch.autograd.Function):
-    @staticmethod
-    def forward(y, geo, norm):
-        return _fan_adj(y, geo, norm)
+def radon_forward(x, geo, norm=None):
+    """Radon transform divided by the device scalar `norm` (None: unnormalised)"""
+    return _Apply.apply(x, ExactPair(geo, norm), False)
 
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        _, ctx.geo, ctx.norm = inputs
 
-    @staticmethod
-    def backward(ctx, g):
-        return _FanFwd.apply(g, ctx.geo, ctx.norm), None, None
+def radon_adjoint(y, geo, norm=None):
+    return _Apply.apply(y, ExactPair(geo, norm), True)
+
+
+def apply_radon(x, geo, scale, adjoint):
+    return _Apply.apply(x, InterpolatingPair(geo, float(scale)), bool(adjoint))
 
 
 def fan_forward(x, geo: FanGeometry, norm=None):
-    return _FanFwd.apply(x, geo, norm)
+    return _Apply.apply(x, FanPair(geo, norm), False)
 
 
 def fan_adjoint(y, geo: FanGeometry, norm=None):
-    return _FanAdj.apply(y, geo, norm)
+    return _Apply.apply(y, FanPair(geo, norm), True)
 
 
 # --------------------------------------------------------------------------- ramp filter
@@ -370,9 +345,7 @@ class _Ramp(torch.autograd.Function):
         use_fft = P <= RAMP_FFT_MAX_P and ENABLE_RAMP_FFT
         if use_fft:
             P, plan, table, filt = _ramp_tables(N, dev)
-        step = 65535
-        for s in range(0, n, step):
-            e = min(n, s + step)
+        for s, e in _chunks(n):
             yy, oo = y.view(n, N, A)[s:e], out.view(n, N, A)[s:e]
             if use_fft:
                 check(_l().dinv_radon_ramp_fft(e - s, N, A, P, ctypes.byref(plan), ptr(table), ptr(filt), ptr(yy), ptr(oo),

@@ -94,8 +94,9 @@ class Tomography(LinearPhysics):
         self._geo = None
 
     def _norm(self):
-        """the operator norm as a DEVICE scalar handed to the kernels (no host read-back per call)"""
-        return self.operator_norm.reshape(1) if self.normalize else None
+        """the operator norm as a DEVICE scalar handed to the kernels (no host read-back per call): the buffer itself, which the
+        operator pair of hip/radon.py may keep beyond a torch.func transform (a view made inside one dies with it)"""
+        return self.operator_norm if self.normalize else None
 
     def _scale_host(self):
         """1/||A|| as a host float for the ApplyRadon branch only; read back once per value of the buffer"""
