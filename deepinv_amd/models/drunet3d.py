@@ -172,8 +172,9 @@ class Ops3d:
         cout, cin = (w5.shape[1], w5.shape[0]) if flip else w5.shape[:2]
         y = Vol(lv, cout, x.t.device)
         # inference: the ReLU temporary of a ResBlock (the one `relu` output; consumed only by the block's second convolution, of the
-        # same channel counts) travels pre-split; training keeps it in fp32 (the backward pass reads its sign)
-        y.presplit = relu and not self.train and min(cout, cin) >= 16 and max(cout, cin) > 16
+        # same channel counts) travels pre-split where the bf16-split kernels run the block; training keeps it in fp32 (the backward
+        # pass reads its sign), and so does fp32 arithmetic (the fp32 kernels neither write nor read the split form)
+        y.presplit = relu and not self.train and not fp32 and min(cout, cin) >= 16 and max(cout, cin) > 16
         # 16 -> 16 channels is ONE 16 x 16 x 4 MFMA tile of the fp32 thin kernel; the bf16-split kernel pads the outputs to its 64-row
         # tile (measured at config 4's level 0: 0.43 ms against 0.32 ms), so those layers take the fp32 kernel in every setting
         thin = cin <= 16 and cout <= 16

@@ -6,8 +6,9 @@ instance at one of its edges; a restatement of every launcher's arithmetic (the 
 and one runner.  Every call goes through ctypes with the product's prototypes (deepinv_amd.hip.drunet._declare) on guarded buffers
 (fft_cases.Guarded).
 
-3-D is left out on purpose: conv3x3x3, conv3x3x3_split and the _3d stride-2 calls are reached per element by the `dgrad3d`,
-`dstride3d` and `gate` kinds of tests/bwd_cases.py (the thin kernel's gate epilogue as well).
+The 3-D forms of these kernels (dinv_conv3x3x3, dinv_conv3x3x3_split, dinv_conv_down2x2_bf16s_3d, dinv_conv_up2x2_bf16s_3d) have a
+table of their own, tests/drunet3d_cases.py, built on the helpers of this module (the buffer helpers below take the guard plane and
+the depth of a drunet3d.Level for it).
 
 Data classes (per case; `Case.classes()`):
 
@@ -685,21 +686,30 @@ def data(c, cls):
 
 
 # ------------------------------------------------------------------ buffers
-def _nan_frame(g, a):
-    """NaN on the whole frame of an activation buffer (interior kept)"""
+def _nan_frame(g, a, guard=0, depth=0):
+    """NaN on the whole frame of an activation buffer (interior kept); guard: pixels in front of the buffer proper (drunet3d.Level);
+    depth: the images are volumes of depth + 2 slices, and the two end slices of each are NaN as well"""
     cb, n, H, W = a.shape[0], g.batch, g.height, g.width
-    av = a[:, g.sl:g.sl + g.np].view(cb, n, g.hp, g.wp, 8)
+    av = a[:, guard + g.sl:guard + g.sl + g.np].view(cb, n, g.hp, g.wp, 8)
     inner = av[:, :, 1:H + 1, 1:W + 1].clone()
     av[:] = float("nan")
-    av[:, :, 1:H + 1, 1:W + 1] = inner
+    if depth:
+        av.view(cb, n // (depth + 2), depth + 2, g.hp, g.wp, 8)[:, :, 1:-1, 1:H + 1, 1:W + 1] = \
+            inner.view(cb, n // (depth + 2), depth + 2, H, W, 8)[:, :, 1:-1]
+    else:
+        av[:, :, 1:H + 1, 1:W + 1] = inner
     return a
 
 
-def in_buf(be, g, imgs, frame="zero", split=False):
-    """a Guarded input buffer [C/8, cs, 8]: zero padding channels, `frame` on the frame, NaN on everything outside [sl, sl + np)"""
-    a = to_buf(g, imgs, "nan")
+def in_buf(be, g, imgs, frame="zero", split=False, guard=0, depth=0):
+    """a Guarded input buffer [C/8, cs, 8]: zero padding channels, `frame` on the frame (depth: and on the end slices of every volume),
+    NaN on everything outside [sl, sl + np) - the guard planes of a drunet3d.Level (guard pixels at each end) included"""
+    a = to_buf(g, imgs, "nan", guard)
+    if guard:
+        a[:, :guard] = float("nan")
+        a[:, g.cs - guard:] = float("nan")
     if frame == "nan":
-        _nan_frame(g, a)
+        _nan_frame(g, a, guard, depth)
     if split:                                         # pre-split: 8 bf16 high parts then 8 bf16 low parts in the same 32 bytes
         hi = a.bfloat16()
         lo = (a - hi.float()).bfloat16()
@@ -708,42 +718,50 @@ def in_buf(be, g, imgs, frame="zero", split=False):
     return gb
 
 
-def masks(g):
-    """(interior, in-range) boolean masks over the cs pixels of a channel-block row"""
+def masks(g, guard=0, depth=0):
+    """(interior, in-range) boolean masks over the cs pixels of a channel-block row; guard: pixels in front of the buffer proper;
+    depth: volumes of depth + 2 slices, whose end slices are no interior"""
+    lo = guard + g.sl
     inside = torch.zeros(g.cs, dtype=torch.bool)
-    inside[g.sl:g.sl + g.np] = True
+    inside[lo:lo + g.np] = True
     inner = torch.zeros(g.cs, dtype=torch.bool)
-    iv = inner[g.sl:g.sl + g.np].view(g.batch, g.hp, g.wp)
-    iv[:, 1:g.height + 1, 1:g.width + 1] = True
+    iv = inner[lo:lo + g.np].view(g.batch, g.hp, g.wp)
+    if depth:
+        iv.view(g.batch // (depth + 2), depth + 2, g.hp, g.wp)[:, 1:-1, 1:g.height + 1, 1:g.width + 1] = True
+    else:
+        iv[:, 1:g.height + 1, 1:g.width + 1] = True
     return inner, inside
 
 
-def write_mask(g, writes):
-    inner, inside = masks(g)
+def write_mask(g, writes, guard=0, depth=0):
+    """the pixels a launch stores to: "all" | "interior" | "rows", or the mask itself"""
+    if isinstance(writes, torch.Tensor):
+        return writes
+    inner, inside = masks(g, guard, depth)
     if writes == "all":
         return inside
     if writes == "interior":
         return inner
     m = torch.zeros(g.cs, dtype=torch.bool)
-    m[g.sl:g.sl + g.np].view(g.batch, g.hp, g.wp)[:, :, 1:g.width + 1] = True       # "rows"
+    m[guard + g.sl:guard + g.sl + g.np].view(g.batch, g.hp, g.wp)[:, :, 1:g.width + 1] = True       # "rows"
     return m
 
 
 PO2 = 0x7FD1C0DE                  # the prefill of words a launch must not write (a NaN no kernel produces; the guards hold POISON)
 
 
-def out_buf(be, g, blocks, owned, writes, lanes=8):
+def out_buf(be, g, blocks, owned, writes, lanes=8, guard=0, depth=0, hold=0):
     """a Guarded output buffer of `blocks` channel blocks of which the launch owns the first `owned` (channels < lanes of them):
-    interior NaN, frame NaN where the launch writes zeros and zero where it never writes, everything else PO2.  Returns (Guarded,
-    the prefill bits, the mask of words the launch may write)"""
-    inner, inside = masks(g)
-    wm = write_mask(g, writes)
+    interior NaN, frame NaN where the launch writes zeros and `hold` (bits; zero unless told) where it never writes, everything else
+    PO2.  Returns (Guarded, the prefill bits, the mask of words the launch may write)"""
+    inner, inside = masks(g, guard, depth)
+    wm = write_mask(g, writes, guard, depth)
     pre = torch.full((blocks, g.cs, 8), PO2, dtype=torch.int32)
     may = torch.zeros((blocks, g.cs, 8), dtype=torch.bool)
     nanbits = torch.tensor(float("nan")).view(torch.int32)
     for b in range(owned):
         fz = pre[b, inside & ~inner]
-        fz[:, :lanes] = 0                             # frame the launch leaves alone: zero, and it keeps those bits (lanes it does
+        fz[:, :lanes] = hold                          # frame the launch leaves alone: zero, and it keeps those bits (lanes it does
         pre[b, inside & ~inner] = fz                  # not own - channels 4 .. 7 of the tail - stay PO2 on the frame as well)
         fw = pre[b, wm & ~inner]
         fw[:, :lanes] = nanbits                       # frame the launch writes: NaN, must come back as exact zeros
@@ -754,16 +772,16 @@ def out_buf(be, g, blocks, owned, writes, lanes=8):
     return gb, pre, may
 
 
-def check_out(c, cls, g, gb, pre, may, owned, lanes=8, frame_poison=False):
+def check_out(c, cls, g, gb, pre, may, owned, lanes=8, frame_poison=False, guard=0, depth=0, writes=None):
     """guards intact; every word the launch may not write keeps its prefill bits; the frame of the owned blocks is exactly zero (or,
-    frame_poison, untouched); returns the buffer as [blocks, cs, 8] on the host"""
+    frame_poison, untouched; with `writes`: the part of it the launch stores to); returns the buffer as [blocks, cs, 8] on the host"""
     assert gb.guards_intact(), f"{c.id}/{cls}: wrote outside the output allocation"
     bits = gb.bits().view(pre.shape)
     bad = (bits != pre) & ~may
     assert not bool(bad.any()), f"{c.id}/{cls}: {int(bad.sum())} words the launch must not write changed (first at {bad.nonzero()[0].tolist()})"
-    inner, inside = masks(g)
+    inner, inside = masks(g, guard, depth)
     if not frame_poison:
-        fr = bits[:owned][:, inside & ~inner][..., :lanes]
+        fr = bits[:owned][:, (inside if writes is None else write_mask(g, writes, guard, depth)) & ~inner][..., :lanes]
         assert not bool(fr.any()), f"{c.id}/{cls}: {int((fr != 0).sum())} frame words are not exact zeros"
     return bits.view(torch.float32)
 
