@@ -18,7 +18,10 @@
 // [S, I, R] and dense_reduce_kernel adds the slices in index order: no atomics, bit-reproducible.  One slice writes `out` itself.
 // The tile constants, the K-slice and workspace rules, the checks, the grid and the dispatch are those of dense_core.hpp, shared
 // with cdense.hip; this file holds the fp32 kernels and what they are given.
+// The Gaussian-mixture patch prior (dinv_gmm_*: scores, classification and the EPLL step) uses the same fp32 product scheme with
+// its own epilogues: its kernels and planning are patch_gmm.hpp, its entry points are at the end of this file.
 #include "dense_core.hpp"
+#include "patch_gmm.hpp"
 
 using namespace dinv;
 
@@ -141,5 +144,68 @@ extern "C" int dinv_dense_apply(const float* in, const float* M, float* out, int
         hipLaunchKernelGGL(dense_reduce_kernel, p.reduce_grid, dim3(256), 0, st, (const float*)workspace, out, p.total, (int)p.S);
         DINV_CHECK_LAUNCH();
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------- Gaussian-mixture patch prior (patch_gmm.hpp)
+extern "C" int dinv_gmm_scores(const float* src, int32_t image, int64_t N, int32_t C, int32_t H, int32_t W, int32_t p, const float* Wt,
+                               const float* m, const float* lam, const float* logw, int32_t K, int32_t d, const float* r,
+                               int32_t epilogue, void* out, dinv_stream_t stream) {
+    const GmmModel g{Wt, m, lam, logw, K, d};
+    GmmPlan pl;
+    if (int e = gmm_check_epilogue("gmm_scores", epilogue)) return e;
+    if (int e = image ? gmm_plan_image("gmm_scores", g, N, C, H, W, p, &pl) : gmm_plan_rows("gmm_scores", g, N, &pl)) return e;
+    if (pl.empty) return 0;
+    DINV_REQUIRE(src && out, "gmm_scores: src and out must be non-null");
+    DINV_REQUIRE((const void*)src != out, "gmm_scores: out must not alias src");
+    DINV_REQUIRE(epilogue != DINV_GMM_SCORES || pl.N * K < ((int64_t)1 << 40), "gmm_scores: a score matrix of %lld x %d is too large",
+                 (long long)pl.N, K);
+    hipStream_t st = (hipStream_t)stream;
+    GmmScoreArgs a{};
+    a.g = g; a.src = src; a.r = r; a.out = out; a.N = pl.N;
+    a.C = C; a.H = H; a.W = W; a.p = image ? p : 1; a.PH = pl.PH; a.PW = pl.PW;
+    a.epilogue = epilogue;
+    if (image) DINV_GMM_LAUNCH_SCORE(true, pl, st, a);
+    else DINV_GMM_LAUNCH_SCORE(false, pl, st, a);
+    return 0;
+}
+
+extern "C" size_t dinv_gmm_epll_workspace_bytes(int64_t B, int32_t C, int32_t H, int32_t W, int32_t p) {
+    return gmm_epll_workspace_bytes(B, C, H, W, p);
+}
+
+extern "C" int dinv_gmm_epll_step(const float* x, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, const float* Wt, const float* m,
+                                  const float* lam, const float* logw, int32_t K, int32_t d, const float* r, const float* a,
+                                  const float* cb, const float* bias, float* out, void* workspace, size_t workspace_bytes,
+                                  dinv_stream_t stream) {
+    const GmmModel g{Wt, m, lam, logw, K, d};
+    GmmPlan pl;
+    if (int e = gmm_plan_image("gmm_epll_step", g, B, C, H, W, p, &pl)) return e;
+    if (pl.empty) return 0;
+    DINV_REQUIRE(x && out && r && a, "gmm_epll_step: x, out, r and a must be non-null");
+    const size_t need = gmm_epll_workspace_bytes(B, C, H, W, p);
+    DINV_REQUIRE(workspace && workspace_bytes >= need, "gmm_epll_step: the workspace holds %zu bytes, %zu are needed "
+                 "(dinv_gmm_epll_workspace_bytes)", workspace_bytes, need);
+    DINV_REQUIRE(aligned16(workspace), "gmm_epll_step: the workspace must be 16-byte aligned");
+    DINV_REQUIRE(2 * (size_t)d * sizeof(float) <= kDefaultLdsBytes, "gmm_epll_step: d = %d is too large for the estimate kernel", d);
+    hipStream_t st = (hipStream_t)stream;
+    float* z = (float*)workspace;
+    int32_t* kstar = (int32_t*)(z + pl.N * d);
+    GmmScoreArgs s{};
+    s.g = g; s.src = x; s.r = r; s.out = kstar; s.N = pl.N;
+    s.C = C; s.H = H; s.W = W; s.p = p; s.PH = pl.PH; s.PW = pl.PW;
+    s.epilogue = DINV_GMM_ARGMAX;
+    DINV_GMM_LAUNCH_SCORE(true, pl, st, s);
+    GmmEstimateArgs e{};
+    e.g = g; e.x = x; e.r = r; e.kstar = kstar; e.z = z; e.N = pl.N;
+    e.C = C; e.H = H; e.W = W; e.p = p; e.PH = pl.PH; e.PW = pl.PW;
+    hipLaunchKernelGGL(gmm_estimate_kernel, dim3((unsigned)ceil_div(pl.N, kGmmEstPatches)), dim3(64), 2 * (size_t)d * sizeof(float), st, e);
+    DINV_CHECK_LAUNCH();
+    GmmAggregateArgs ag{};
+    ag.z = z; ag.a = a; ag.cb = cb; ag.bias = bias; ag.out = out; ag.total = B * C * H * W;
+    ag.d = d; ag.C = C; ag.H = H; ag.W = W; ag.p = p; ag.PH = pl.PH; ag.PW = pl.PW;
+    const int64_t blocks = ceil_div(ag.total, 256);
+    hipLaunchKernelGGL(gmm_aggregate_kernel, dim3((unsigned)(blocks > 65536 ? 65536 : blocks)), dim3(256), 0, st, ag);
+    DINV_CHECK_LAUNCH();
     return 0;
 }

@@ -10,8 +10,8 @@
 using namespace dinv;
 
 extern "C" const char* dinv_last_error(void) { return err_buf(); }
-// the ABI version (16: + dinv_cdense_*, dinv_cstructured_*)
-extern "C" int dinv_version(void) { return 17; }
+// the ABI version (the history is beside the declaration in include/deepinv_amd.h)
+extern "C" int dinv_version(void) { return 18; }
 extern "C" int dinv_device_count(int* count) {
     int c = 0;
     hipError_t e = hipGetDeviceCount(&c);

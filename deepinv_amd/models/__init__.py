@@ -4,3 +4,4 @@ from .tv import TVDenoiser, TVL1Denoiser
 from .dncnn import DnCNN
 from .tgv import TGVDenoiser
 from .anscombe import AnscombeDenoiser, generalized_anscombe_transform, inverse_generalized_anscombe_transform
+from .epll import EPLLDenoiser

@@ -12,3 +12,4 @@ from .phase_retrieval import (default_preprocessing, correct_global_phase, cosin
                               spectral_methods_wrapper)
 from . import linear
 from . import phase_retrieval
+from .epll import EPLL, GaussianMixtureModel

@@ -35,7 +35,7 @@ typedef void* dinv_stream_t; /* hipStream_t */
 /* library / error                                                            */
 /* ------------------------------------------------------------------------- */
 const char* dinv_last_error(void);
-int dinv_version(void);   /* 17 = this header (adds the ptychography entry points dinv_ptycho_apply and dinv_ptycho_workspace_bytes); 16: (adds the complex64 phase-retrieval entry points dinv_cdense_apply and dinv_cstructured_apply); 15: (adds the DST-I / StructuredRandom entry points dinv_dst1, dinv_structured_apply and the dense fp32 product dinv_dense_apply); 14: (adds dinv_poisson_noise and dinv_fidelity_pointwise); 13: (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
+int dinv_version(void);   /* 18 = this header (adds the Gaussian-mixture patch prior: dinv_gmm_scores, dinv_gmm_epll_step and dinv_gmm_epll_workspace_bytes); 17: (adds the ptychography entry points dinv_ptycho_apply and dinv_ptycho_workspace_bytes); 16: (adds the complex64 phase-retrieval entry points dinv_cdense_apply and dinv_cstructured_apply); 15: (adds the DST-I / StructuredRandom entry points dinv_dst1, dinv_structured_apply and the dense fp32 product dinv_dense_apply); 14: (adds dinv_poisson_noise and dinv_fidelity_pointwise); 13: (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
 /* number of visible HIP devices (0 when no GPU): used by the host to fail loudly */
 int dinv_device_count(int* count);
 
@@ -841,6 +841,36 @@ int dinv_ptycho_apply(const float* x, float* out, const void* probe, int32_t pro
                       int32_t n_img, int32_t H, int32_t W, int32_t op, int32_t epilogue, float eps, int32_t group,
                       const dinv_fft_plan* plan_w, const void* table_w_dev, const dinv_fft_plan* plan_h, const void* table_h_dev,
                       void* workspace, size_t workspace_bytes, dinv_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
+/* Gaussian-mixture patch prior and EPLL (csrc/patch_gmm.hpp; reference deepinv/optim/utils.py:261-312 GaussianMixtureModel,  */
+/* deepinv/optim/epll.py:167-229 EPLL._reconstruction_step)                                                                  */
+/* ------------------------------------------------------------------------- */
+/* The model in its eigenbasis, Sigma_k = Q_k diag(lam_k) Q_k^T, fp32 on the device:
+ *   Wt [K dp, d] the stacked Q_k^T (row k dp + i = eigenvector i of component k), m [K dp] = Q_k^T mu_k, lam [K dp], logw [K] or
+ *   null; dp = d rounded up to a multiple of 4, and the dp - d padding rows of a component hold Wt = 0, m = 0, lam = 1.
+ * A patch x under component k with regularisation r (Sigma_k + r I):
+ *   score_k = logw_k - 1/2 sum_i log(lam_ki + r) - 1/2 sum_i ((Q_k^T x)_i - m_ki)^2 / (lam_ki + r) - d/2 log 2 pi
+ * lam_ki + r > 0 is the caller's contract.
+ * dinv_gmm_scores: the product on the fp32 matrix cores, folded into the scores in registers.
+ *   image = 0: src is [N, d] rows; r is null or one float.   image = 1: src is an image [N, C, H, W] (N = the batch), its patches
+ *   are all p x p windows in the order (b, y0, x0) with entries in the order (c, dy, dx), d = C p^2; r is null or [N] floats.
+ *   epilogue SCORES: out is float [patches, K];  ARGMAX: out is int32 [patches], the first index of the largest score;
+ *   NLL: out is float [patches], -log sum_k exp(score_k).
+ * dinv_gmm_epll_step: one half-quadratic step on x [B, C, H, W] in three launches: k* = argmax_k score_k per patch,
+ *   z = Q_k* diag(lam / (lam + r)) Q_k*^T x per patch, and per pixel the sum of the covering patch entries in ascending (y0, x0)
+ *   over their number, out = a[b] x~ + cb[b] bias (bias null: no bias; cb null: 1).  r, a, cb are [B] device floats.  No atomics:
+ *   bitwise reproducible.  out may be x or bias.  The workspace holds z [N, d] and k* [N]. */
+#define DINV_GMM_SCORES 0
+#define DINV_GMM_ARGMAX 1
+#define DINV_GMM_NLL 2
+int dinv_gmm_scores(const float* src, int32_t image, int64_t N, int32_t C, int32_t H, int32_t W, int32_t p, const float* Wt,
+                    const float* m, const float* lam, const float* logw, int32_t K, int32_t d, const float* r, int32_t epilogue,
+                    void* out, dinv_stream_t stream);
+size_t dinv_gmm_epll_workspace_bytes(int64_t B, int32_t C, int32_t H, int32_t W, int32_t p);
+int dinv_gmm_epll_step(const float* x, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, const float* Wt, const float* m,
+                       const float* lam, const float* logw, int32_t K, int32_t d, const float* r, const float* a, const float* cb,
+                       const float* bias, float* out, void* workspace, size_t workspace_bytes, dinv_stream_t stream);
 
 #ifdef __cplusplus
 }
