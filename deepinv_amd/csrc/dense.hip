@@ -19,9 +19,11 @@
 // The tile constants, the K-slice and workspace rules, the checks, the grid and the dispatch are those of dense_core.hpp, shared
 // with cdense.hip; this file holds the fp32 kernels and what they are given.
 // The Gaussian-mixture patch prior (dinv_gmm_*: scores, classification and the EPLL step) uses the same fp32 product scheme with
-// its own epilogues: its kernels and planning are patch_gmm.hpp, its entry points are at the end of this file.
+// its own epilogues: its kernels and planning are patch_gmm.hpp, its entry points are at the end of this file.  The sums of its EM
+// step (dinv_gmm_posterior, dinv_gmm_moments) follow them: gmm_moments.hpp.
 #include "dense_core.hpp"
 #include "patch_gmm.hpp"
+#include "gmm_moments.hpp"
 
 using namespace dinv;
 
@@ -206,6 +208,58 @@ extern "C" int dinv_gmm_epll_step(const float* x, int64_t B, int32_t C, int32_t 
     ag.d = d; ag.C = C; ag.H = H; ag.W = W; ag.p = p; ag.PH = pl.PH; ag.PW = pl.PW;
     const int64_t blocks = ceil_div(ag.total, 256);
     hipLaunchKernelGGL(gmm_aggregate_kernel, dim3((unsigned)(blocks > 65536 ? 65536 : blocks)), dim3(256), 0, st, ag);
+    DINV_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------- EM for the Gaussian mixture (patch_gmm.hpp, gmm_moments.hpp)
+extern "C" int dinv_gmm_posterior(const float* x, int64_t N, const float* Wt, const float* m, const float* lam, const float* logw,
+                                  int32_t K, int32_t d, float* beta, float* nll, dinv_stream_t stream) {
+    const GmmModel g{Wt, m, lam, logw, K, d};
+    GmmPlan pl;
+    if (int e = gmm_plan_rows("gmm_posterior", g, N, &pl)) return e;
+    if (pl.empty) return 0;
+    DINV_REQUIRE(logw, "gmm_posterior: the log weights must be non-null: a responsibility carries its component's weight");
+    DINV_REQUIRE(x && beta && nll, "gmm_posterior: x, beta and nll must be non-null");
+    DINV_REQUIRE(x != beta && x != nll && beta != nll, "gmm_posterior: beta and nll must not alias x or each other");
+    DINV_REQUIRE(pl.N * K < ((int64_t)1 << 40), "gmm_posterior: a responsibility matrix of %lld x %d is too large", (long long)pl.N, K);
+    hipStream_t st = (hipStream_t)stream;
+    GmmScoreArgs a{};
+    a.g = g; a.src = x; a.r = nullptr; a.out = beta; a.nll = nll; a.N = pl.N;
+    a.p = 1;
+    a.epilogue = kGmmPosterior;
+    DINV_GMM_LAUNCH_SCORE(false, pl, st, a);
+    return 0;
+}
+
+extern "C" size_t dinv_gmm_moments_workspace_bytes(int64_t N, int32_t K, int32_t d, int32_t chunk_rows) {
+    return gmm_moments_workspace_bytes(N, K, d, chunk_rows);
+}
+
+extern "C" int dinv_gmm_moments(const float* x, const float* beta, const float* c, const float* nll, int64_t N, int32_t K, int32_t d,
+                                int32_t chunk_rows, double* S0, double* S1, double* S2, double* obj, void* workspace,
+                                size_t workspace_bytes, dinv_stream_t stream) {
+    GmmMomentsPlan pl;
+    if (int e = gmm_moments_plan("gmm_moments", N, K, d, chunk_rows, &pl)) return e;
+    if (pl.empty) return 0;
+    DINV_REQUIRE(x && beta && c, "gmm_moments: x, beta and c must be non-null");
+    DINV_REQUIRE(S0 && S1 && S2, "gmm_moments: the accumulators S0, S1 and S2 must be non-null");
+    DINV_REQUIRE(!nll || obj, "gmm_moments: nll is given, so the accumulator obj must be non-null");
+    DINV_REQUIRE(workspace && workspace_bytes >= pl.ws_bytes, "gmm_moments: the workspace holds %zu bytes, %zu are needed "
+                 "(dinv_gmm_moments_workspace_bytes)", workspace_bytes, pl.ws_bytes);
+    DINV_REQUIRE(aligned16(workspace), "gmm_moments: the workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    GmmMomentsArgs a{};
+    a.x = x; a.beta = beta; a.c = c; a.ws = (float*)workspace;
+    a.N = N; a.chunk_rows = pl.chunk_rows; a.chunks = pl.chunks;
+    a.K = K; a.d = d; a.T = pl.T; a.nblk = pl.nblk;
+    const dim3 grid((unsigned)pl.items, (unsigned)pl.chunks, (unsigned)K);
+    DINV_GMM_LAUNCH_MOMENTS(pl, grid, st, a);
+    GmmReduceArgs r{};
+    r.ws = a.ws; r.nll = nll; r.S0 = S0; r.S1 = S1; r.S2 = S2; r.obj = obj;
+    r.N = N; r.chunks = pl.chunks; r.total = (int64_t)K * pl.nblk * 1024;
+    r.K = K; r.d = d; r.T = pl.T; r.nblk = pl.nblk;
+    hipLaunchKernelGGL(gmm_moments_reduce_kernel, dim3((unsigned)(r.total / 256 + 1)), dim3(256), 0, st, r);
     DINV_CHECK_LAUNCH();
     return 0;
 }

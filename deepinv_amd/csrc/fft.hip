@@ -11,7 +11,7 @@ using namespace dinv;
 
 extern "C" const char* dinv_last_error(void) { return err_buf(); }
 // the ABI version (the history is beside the declaration in include/deepinv_amd.h)
-extern "C" int dinv_version(void) { return 18; }
+extern "C" int dinv_version(void) { return 19; }
 extern "C" int dinv_device_count(int* count) {
     int c = 0;
     hipError_t e = hipGetDeviceCount(&c);

@@ -26,16 +26,22 @@
 // Operand sources: rows [N, d] read from memory (patch n of a wave tile is row n), or an image [B, C, H, W] staged in LDS as a
 // tile of (4 NP + p - 1) x (32 + p - 1) pixels per channel, where entry (c, dy, dx) of a patch is a constant offset and
 // consecutive lanes are consecutive x0; the patch matrix never exists.  The per-image table
-// logw_k - 1/2 sum_i log(lam_ki + r) - d/2 log 2 pi is computed by each workgroup into LDS in its prologue.  Epilogues: SCORES
+// c_k = logw_k - 1/2 sum_i log(lam_ki + r) - d/2 log 2 pi is computed by each workgroup into LDS in its prologue, in fp64 from the
+// fp32 lam_ki + r, and kept as two floats c_k = hi_k + lo_k: score = hi + (lo - q / 2).  A single float at |c_k| of about 100
+// is off by up to 8e-6, the same for every patch of a component, which does not average out in a mean log-likelihood (the
+// objective of EM); with the pair the only roundings left are per patch.  Epilogues: SCORES
 // stores [N, K]; ARGMAX keeps a running best over ascending k with strict > (the lowest index wins a tie, like torch.max) and
-// stores int32 [N]; NLL keeps an online log-sum-exp and stores -log sum_k exp(score_k) [N].
+// stores int32 [N]; NLL keeps an online log-sum-exp and stores -log sum_k exp(score_k) [N]; POSTERIOR (rows mode, behind
+// dinv_gmm_posterior only) is NLL that also stores the responsibilities exp(score_k - lse) [N, K]: the two half waves hold the
+// same scores, so half h stores the scores of the components k = h mod 2 and rescales exactly those entries of its own row once
+// lse is known - one launch, no exchange, and -lse is computed by the instructions of NLL.
 // gmm_estimate_kernel: one wave per patch, z from the gathered Q_k* in two d x d matrix-vector products through LDS -> [N, d].
 // gmm_aggregate_kernel: one thread per pixel adds the <= p^2 covering patch entries in ascending (y0, x0), divides by the closed-
 // form multiplicity and applies out = a[b] x~ + cb[b] bias.  No atomics anywhere: results are bitwise reproducible, and a patch's
 // score does not depend on NP or on the image it is batched with.
 //
 // Limits (DINV_REQUIRE): d = C p^2 (image mode); H, W >= p; K >= 1, d >= 1, K dp < 2^31; patches < 2^31; the LDS of a workgroup
-// (4 (K + d + C (4 NP + p - 1)(32 + p - 1)) bytes) within 160 KB, which admits d = 192 (p = 8, C = 3) with K in the thousands.
+// (4 (2 K + d + C (4 NP + p - 1)(32 + p - 1)) bytes) within 160 KB, which admits d = 192 (p = 8, C = 3) with K in the thousands.
 // lam + r > 0 is the caller's contract (the Python layer checks it when it builds the operands).  Nothing is launched for an empty
 // batch.
 #pragma once
@@ -46,7 +52,8 @@ namespace dinv {
 constexpr int kGmmWaves = 4;             // waves per workgroup of the score kernel
 constexpr int kGmmTargetGroups = 256;    // one workgroup per compute unit of an MI355X before a wave takes more patch tiles
 constexpr int kGmmEstPatches = 4;        // patches per workgroup of the estimate kernel
-constexpr float kLog2Pi = 1.8378770664093453f;
+constexpr double kLog2Pi = 1.8378770664093453;
+constexpr int kGmmPosterior = DINV_GMM_NLL + 1;     // the epilogue of dinv_gmm_posterior: not one dinv_gmm_scores accepts
 
 // rows per component in Wt, m and lam
 __host__ __device__ inline int gmm_dp(int d) { return (d + 3) & ~3; }
@@ -64,6 +71,7 @@ struct GmmScoreArgs {
     const float* src;      // rows [N, d] or image [B, C, H, W]
     const float* r;        // [B] (rows: [1]) or null
     void* out;
+    float* nll;            // POSTERIOR: [N] beside the responsibilities in out
     int64_t N;             // rows mode: rows
     int C, H, W, p, PH, PW;
     int epilogue;
@@ -74,15 +82,18 @@ __global__ __launch_bounds__(256) void gmm_score_kernel(GmmScoreArgs a) {
     DINV_DYN_LDS(float, lds);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, j = lane & 31, h = lane >> 5;
     const int d = a.g.d, K = a.g.K, dk = (d + 1) & ~1, dp = gmm_dp(d);
-    float* cst = lds;                                      // [K]
-    int* offk = reinterpret_cast<int*>(lds + K);           // [dk]
-    float* tile = lds + K + dk;                            // [C, TYP, TXP]
+    float* cst = lds;                                      // [2, K]: hi, lo
+    int* offk = reinterpret_cast<int*>(lds + 2 * K);       // [dk]
+    float* tile = lds + 2 * K + dk;                        // [C, TYP, TXP]
     const int b = IMAGE ? (int)blockIdx.z : 0;
     const float r = a.r ? a.r[b] : 0.f;
     for (int k = tid; k < K; k += 256) {
-        float s = 0.f;
-        for (int i = 0; i < d; ++i) s += logf(a.g.lam[(int64_t)k * dp + i] + r);
-        cst[k] = (a.g.logw ? a.g.logw[k] : 0.f) - 0.5f * s - 0.5f * (float)d * kLog2Pi;
+        double s = 0.0;
+        for (int i = 0; i < d; ++i) s += log((double)(a.g.lam[(int64_t)k * dp + i] + r));
+        const double c = (a.g.logw ? (double)a.g.logw[k] : 0.0) - 0.5 * s - 0.5 * (double)d * kLog2Pi;
+        const float hi = (float)c;
+        cst[k] = hi;
+        cst[K + k] = (float)(c - (double)hi);
     }
     const int TYP = kGmmWaves * NP + a.p - 1, TXP = 32 + a.p - 1;
     const int tx0 = (int)blockIdx.x * 32, ty0 = (int)blockIdx.y * kGmmWaves * NP;
@@ -175,7 +186,7 @@ __global__ __launch_bounds__(256) void gmm_score_kernel(GmmScoreArgs a) {
         for (int k = k_lo; k <= k_hi; ++k) {
             const int64_t lo = (int64_t)k * dp - g0, hi = lo + dp;     // rows [lo, hi) of the tile belong to component k
             const bool ends = hi <= 32;
-            const float c = cst[k];
+            const float chi = cst[k], clo = cst[K + k];
 #pragma unroll
             for (int q = 0; q < NP; ++q)
                 if (q < na) {
@@ -190,17 +201,29 @@ __global__ __launch_bounds__(256) void gmm_score_kernel(GmmScoreArgs a) {
                     }
                     if (!ends) { carry[q] = qf; continue; }
                     carry[q] = 0.f;
-                    const float score = c - 0.5f * (qf + __shfl_xor(qf, 32));
+                    const float score = chi + (clo - 0.5f * (qf + __shfl_xor(qf, 32)));
                     if (a.epilogue == DINV_GMM_SCORES) {
                         if (h == 0 && valid[q]) static_cast<float*>(a.out)[n[q] * K + k] = score;
                     } else if (a.epilogue == DINV_GMM_ARGMAX) {
                         if (score > best[q]) { best[q] = score; bestk[q] = k; }
                     } else {
+                        if (a.epilogue == kGmmPosterior && (k & 1) == h && valid[q]) static_cast<float*>(a.out)[n[q] * K + k] = score;
                         if (score > best[q]) { sum[q] = sum[q] * expf(best[q] - score) + 1.f; best[q] = score; }
                         else if (score > -INFINITY) sum[q] += expf(score - best[q]);      // a zero weight adds nothing
                     }
                 }
         }
+    }
+    if (a.epilogue == kGmmPosterior) {
+#pragma unroll
+        for (int q = 0; q < NP; ++q)
+            if (q < na && valid[q]) {
+                const float lse = best[q] + logf(sum[q]);
+                float* row = static_cast<float*>(a.out) + n[q] * K;
+                for (int k = h; k < K; k += 2) row[k] = expf(row[k] - lse);      // exp(-inf - lse) = 0: a zero weight
+                if (h == 0) a.nll[n[q]] = -lse;
+            }
+        return;
     }
     if (h != 0) return;
 #pragma unroll
@@ -311,7 +334,7 @@ inline int gmm_np(int64_t groups_at[3]) {
 
 inline size_t gmm_score_lds(const GmmModel& g, int C, int p, int np, bool image) {
     const int dk = (g.d + 1) & ~1;
-    size_t words = (size_t)g.K + dk;
+    size_t words = 2 * (size_t)g.K + dk;
     if (image) words += (size_t)C * (kGmmWaves * np + p - 1) * (32 + p - 1);
     return words * sizeof(float);
 }

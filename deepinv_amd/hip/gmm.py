@@ -1,7 +1,9 @@
 """ctypes wrapper of the Gaussian-mixture patch prior of csrc/patch_gmm.hpp (entry points in csrc/dense.hip; include/deepinv_amd.h,
 dinv_gmm_*): component scores, classification and negative log-likelihood of patches on the fp32 matrix cores, and the EPLL
-half-quadratic step (classify, estimate, aggregate) in three launches.  The launch goes to the current stream of the operands'
-device.  fp32 only.
+half-quadratic step (classify, estimate, aggregate) in three launches; and the sums of an expectation-maximisation step
+(csrc/gmm_moments.hpp): responsibilities in one launch (:func:`posterior_rows`), the centred weighted moments of every component
+in two (:func:`accumulate_moments`), and the M-step formulas on the downloaded fp64 sums (:func:`em_finalise`, pure torch).  The
+launch goes to the current stream of the operands' device.  fp32 only.
 
 The model is handed to the kernels in its eigenbasis (:class:`Operands`): ``Sigma_k = Q_k diag(lam_k) Q_k^T`` from one fp64
 ``eigh`` on the host, rounded to fp32 once, so that the regularisation ``Sigma_k + r I`` of a half-quadratic step is a runtime
@@ -27,6 +29,10 @@ def _declare(l):
     l.dinv_gmm_epll_workspace_bytes.restype = sz
     l.dinv_gmm_epll_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
     l.dinv_gmm_epll_step.argtypes = [vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
+    l.dinv_gmm_posterior.argtypes = [vp, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp]
+    l.dinv_gmm_moments_workspace_bytes.restype = sz
+    l.dinv_gmm_moments_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    l.dinv_gmm_moments.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
 
 
 def _l():
@@ -190,6 +196,101 @@ def epll_step(ops: Operands, x: torch.Tensor, p: int, r, a, cb=None, bias=None) 
     check(l.dinv_gmm_epll_step(ptr(x), B, C, H, W, p, ptr(ops.Wt), ptr(ops.m), ptr(ops.lam), ptr(ops.logw), ops.K, ops.d, ptr(r),
                                ptr(a), ptr(cb), ptr(bias), ptr(out), ptr(ws), nbytes, stream_ptr(x.device)))
     return out
+
+
+# ---------------------------------------------------------------------- expectation-maximisation
+def _rows(ops_d: int, x, dev_of):
+    require_hip(x, dev_of)
+    _refuse_grad(x)
+    if x.dim() != 2 or x.shape[1] != ops_d:
+        raise ValueError(f"expected rows [N, {ops_d}], got shape {tuple(x.shape)}")
+    return _input(x, "the input")
+
+
+def posterior_rows(ops: Operands, x: torch.Tensor):
+    """the E-step on rows ``x`` [N, d] under the unregularised model, one launch: ``(beta [N, K], nll [N])`` with
+    ``beta_nk = exp(score_nk - lse_n)`` and ``nll_n = -lse_n``, bitwise :func:`scores_rows` with ``NLL``"""
+    x = _rows(ops.d, x, ops.Wt)
+    _reg(ops, None, 1, x.device)
+    N = x.shape[0]
+    beta = torch.empty((N, ops.K), dtype=torch.float32, device=x.device)
+    nll = torch.empty((N,), dtype=torch.float32, device=x.device)
+    if N:
+        check(_l().dinv_gmm_posterior(ptr(x), N, ptr(ops.Wt), ptr(ops.m), ptr(ops.lam), ptr(ops.logw), ops.K, ops.d, ptr(beta),
+                                      ptr(nll), stream_ptr(x.device)))
+    return beta, nll
+
+
+@dataclass
+class Moments:
+    """the running fp64 device accumulators of one EM step: ``S0`` [K], ``S1`` [K, d], ``S2`` [K, d, d] (the sums of
+    :func:`accumulate_moments`, centred at its ``c``) and ``obj`` [1], the sum of the negative log-likelihoods"""
+    S0: torch.Tensor
+    S1: torch.Tensor
+    S2: torch.Tensor
+    obj: torch.Tensor
+    flat: torch.Tensor             # the one buffer the four are views of, so that a step downloads them in one copy
+
+    @classmethod
+    def of(cls, flat: torch.Tensor, K: int, d: int):
+        S0, S1, S2, obj = flat.split([K, K * d, K * d * d, 1])
+        return cls(S0, S1.view(K, d), S2.view(K, d, d), obj, flat)
+
+    @classmethod
+    def zeros(cls, K: int, d: int, device):
+        return cls.of(torch.zeros(K + K * d + K * d * d + 1, dtype=torch.float64, device=device), K, d)
+
+    def cpu(self):
+        """the accumulators on the host, by one copy"""
+        return Moments.of(self.flat.cpu(), *self.S1.shape)
+
+
+def accumulate_moments(acc: Moments, x: torch.Tensor, beta: torch.Tensor, c: torch.Tensor, nll: torch.Tensor = None,
+                       chunk_rows: int = 0) -> Moments:
+    """adds the sums of one batch to ``acc``, two launches: ``S0_k += sum_n beta_nk``, ``S1_k += sum_n beta_nk (x_n - c_k)``,
+    ``S2_k += sum_n beta_nk (x_n - c_k)(x_n - c_k)^T`` and - with ``nll`` - ``obj += sum_n nll_n``.  ``x`` [N, d], ``beta`` [N, K],
+    ``c`` [K, d] fp32 on the device; ``chunk_rows`` 0 (automatic) or a multiple of 32 forces the rows per fp32 partial sum."""
+    if acc.S1.dim() != 2:
+        raise ValueError(f"the accumulator S1 is [K, d], got shape {tuple(acc.S1.shape)}")
+    K, d = acc.S1.shape
+    got = tuple(tuple(t.shape) for t in (acc.S0, acc.S2, acc.obj))
+    if got != ((K,), (K, d, d), (1,)):
+        raise ValueError(f"the accumulators are S0 [{K}], S1 [{K}, {d}], S2 [{K}, {d}, {d}] and obj [1], got S0, S2, obj of shapes {got}")
+    x = _rows(d, x, acc.S0)
+    require_hip(x, acc.S0, acc.S1, acc.S2, acc.obj, beta, c, nll)
+    N = x.shape[0]
+    if tuple(beta.shape) != (N, K) or tuple(c.shape) != (K, d) or (nll is not None and tuple(nll.shape) != (N,)):
+        raise ValueError(f"expected beta [{N}, {K}], c [{K}, {d}] and nll [{N}], got {tuple(beta.shape)}, {tuple(c.shape)}"
+                         + ("" if nll is None else f", {tuple(nll.shape)}"))
+    beta, c = _input(beta, "beta"), _input(c, "c")
+    nll = None if nll is None else _input(nll, "nll")
+    for t in (acc.S0, acc.S1, acc.S2, acc.obj):
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise TypeError("the accumulators are contiguous fp64 tensors (Moments.zeros)")
+    if N == 0:
+        return acc
+    l = _l()
+    nbytes = l.dinv_gmm_moments_workspace_bytes(N, K, d, chunk_rows)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    check(l.dinv_gmm_moments(ptr(x), ptr(beta), ptr(c), ptr(nll), N, K, d, chunk_rows, ptr(acc.S0), ptr(acc.S1), ptr(acc.S2),
+                             ptr(acc.obj), ptr(ws), nbytes, stream_ptr(x.device)))
+    return acc
+
+
+def em_finalise(S0, S1, S2, c, n: int, cov_regularization: float):
+    """the M-step in fp64 from the centred sums: ``(weights [K], mu [K, d], cov [K, d, d])``.  The raw moments are recovered,
+    ``sum beta x = S1 + S0 c`` and ``sum beta x x^T = S2 + c S1^T + S1 c^T + S0 c c^T``, and the reference's formulas applied to them
+    literally (deepinv/optim/utils.py:403-410 and 361-363): the mass clamped from below at 1e-5, ``mu = . / w``,
+    ``cov = . / w - mu mu^T``, ``weights = w / n`` and ``+ cov_regularization I`` - so a clamped component follows the reference."""
+    S0, S1, S2, c = (t.detach().to(torch.float64) for t in (S0, S1, S2, c))
+    first = S1 + S0[:, None] * c
+    cS1 = c[:, :, None] * S1[:, None, :]
+    second = S2 + cS1 + cS1.transpose(1, 2) + S0[:, None, None] * c[:, :, None] * c[:, None, :]
+    w = torch.maximum(S0, torch.tensor(1e-5).to(S0))                  # (an fp32 1e-5, as the reference builds it)
+    mu = first / w[:, None]
+    cov = second / w[:, None, None] - mu[:, :, None] * mu[:, None, :]
+    cov = cov + cov_regularization * torch.eye(c.shape[1])[None].to(cov)        # (an identity of cov's dtype: not rounded)
+    return w / n, mu, cov
 
 
 def multiplicity(H: int, W: int, p: int) -> torch.Tensor:

@@ -1,5 +1,6 @@
 """Gaussian-mixture patch prior and Expected Patch Log-Likelihood reconstruction (reference deepinv/optim/utils.py:137-312
-``GaussianMixtureModel`` without ``fit``, deepinv/optim/epll.py ``EPLL``) on the kernels of csrc/patch_gmm.hpp.
+``GaussianMixtureModel`` with ``fit``, deepinv/optim/epll.py ``EPLL``) on the kernels of csrc/patch_gmm.hpp and
+csrc/gmm_moments.hpp.
 
 One change from the reference: a covariance is decomposed once, ``Sigma_k = Q_k diag(lam_k) Q_k^T`` (fp64 ``eigh`` on the host),
 and the regularised model ``Sigma_k + r I`` of a half-quadratic step is the same operands with the runtime scalar ``r``: nothing is
@@ -30,7 +31,9 @@ def _per_image(v, B, name):
 
 class GaussianMixtureModel(nn.Module):
     r"""Gaussian mixture model: its component log-likelihoods, negative log-likelihood and classification on the fp32 matrix
-    cores.  Parameter estimation (``fit``) is not implemented.
+    cores, and their estimation from data by expectation-maximisation (:meth:`fit`): per batch the responsibilities in one
+    launch and the centred weighted moments of every component in two, the M-step formulas in fp64 on the host once per
+    iteration.
 
     The kernels read a packed copy of the parameters that is rebuilt when they change.  Change them through ``set_cov``,
     ``set_weights``, ``load_state_dict`` or by rebinding ``.data`` (as the reference's ``fit`` does); after an in-place write through
@@ -58,6 +61,7 @@ class GaussianMixtureModel(nn.Module):
         self._logdet_cov_reg = nn.Parameter(self._weights.clone(), requires_grad=False)
         self._eig = None          # (key, lam fp64 [K, d], Q fp64 [K, d, d]) of the current covariance
         self._ops = None          # (key, hip.gmm.Operands) of the current covariance, means and weights
+        self._mu_host = None      # (key, the means on the host): fit keeps the copy it uploaded
         self.set_cov(self._cov)
 
     # ------------------------------------------------------------------ the eigendecomposition and what derives from it
@@ -91,7 +95,7 @@ class GaussianMixtureModel(nn.Module):
         ``load_state_dict``, a rebound ``.data`` and in-place operations on a parameter itself; they cannot notice an in-place
         write made through ``.data`` (``gmm.mu.data[0] = v``, ``gmm._cov.data.mul_(2)``), which bumps no version counter.  Call
         this after such a write."""
-        self._eig = self._ops = None
+        self._eig = self._ops = self._mu_host = None
 
     def operands(self, regularized: bool) -> G.Operands:
         """the kernels' operands on the parameters' device, rebuilt when a parameter changed (see :meth:`invalidate` for the one
@@ -146,9 +150,88 @@ class GaussianMixtureModel(nn.Module):
         self.set_weights(self._weights)
         return out
 
-    def fit(self, *args, **kwargs):
-        raise NotImplementedError("GaussianMixtureModel.fit (EM) is not implemented in deepinv_amd: load fitted parameters with "
-                                  "load_state_dict")
+    # ------------------------------------------------------------------ expectation-maximisation
+    def _batch(self, batch, rows: int = None):
+        """a batch of the dataloader (its first ``rows`` rows) as fp32 rows [n, dimension] beside the parameters
+        (``x.to(self.mu)``)"""
+        x = batch[0] if isinstance(batch, (tuple, list)) else batch
+        if not isinstance(x, torch.Tensor):
+            raise TypeError(f"fit: a batch is a tensor [n, {self.dimension}] or a tuple or list whose first element is one, got "
+                            f"{type(x).__name__}")
+        if x.dim() != 2 or x.shape[1] != self.dimension:
+            raise ValueError(f"fit: a batch holds rows [n, {self.dimension}], got shape {tuple(x.shape)}")
+        x = x.detach()[:rows].to(self.mu)
+        if x.dtype != torch.float32:
+            raise TypeError(f"fit: the kernels are fp32 and a batch takes the parameters' dtype, {x.dtype}: convert the model with "
+                            ".float()")
+        return x
+
+    def _set_mu(self, mu_host):
+        """rebinds the means to the upload of ``mu_host`` and keeps the host copy for the next M-step"""
+        mu_host = mu_host.detach().to("cpu", self.mu.dtype).contiguous()
+        self.mu.data = mu_host.to(self.mu.device)
+        self.invalidate()
+        self._mu_host = (self._key(self.mu), mu_host)
+
+    def _EM_step(self, dataloader, verbose: bool = False, cov_regularization: float = 0.0):
+        """one EM iteration: per batch three launches into the fp64 device accumulators, then one download and the M-step on
+        the host; ``(weights, mu, cov + cov_regularization I, objective)`` in fp64 on the host.  ``verbose`` is accepted in the
+        reference's position and prints nothing: ``fit`` reports per iteration."""
+        ops = self.operands(False)
+        c = self.mu.detach().float().contiguous()
+        if self._mu_host is None or self._mu_host[0] != self._key(self.mu):      # means set by someone else: one small download
+            self._mu_host = (self._key(self.mu), self.mu.detach().cpu())
+        c_host = self._mu_host[1]
+        acc = G.Moments.zeros(self.n_components, self.dimension, c.device)
+        n = 0
+        for batch in dataloader:
+            x = self._batch(batch)
+            n += x.shape[0]
+            beta, nll = G.posterior_rows(ops, x)
+            G.accumulate_moments(acc, x, beta, c, nll)
+        if n == 0:
+            raise ValueError("fit: the dataloader yielded no rows")
+        host = acc.cpu()
+        weights, mu, cov = G.em_finalise(host.S0, host.S1, host.S2, c_host, n, cov_regularization)
+        return weights, mu, cov, float(host.obj) / n
+
+    def fit(self, dataloader, max_iters: int = 100, stopping_criterion: float = None, data_init: bool = True,
+            cov_regularization: float = 1e-5, verbose: bool = False):
+        r"""Batched expectation-maximisation, the reference's ``fit`` (deepinv/optim/utils.py:314-412).
+
+        :param dataloader: any iterable of batches ``[n, dimension]``, or of tuples or lists whose first element is one; it is
+            iterated once per iteration, and batches are moved to the parameters' device
+        :param int max_iters: maximum number of iterations
+        :param float stopping_criterion: stop when the objective decreases by less than this; ``None``: ``max_iters`` iterations
+        :param bool data_init: initialise the means with the first ``n_components`` rows (a shorter first batch is filled up
+            with ``randn * std + mean`` of its rows); ``False`` starts from the current parameters
+        :param float cov_regularization: added to the diagonal of every new covariance
+        :param bool verbose: print the objective of every iteration
+        """
+        if dataloader is None:
+            raise NotImplementedError("GaussianMixtureModel.fit needs an iterable of [n, d] batches; fitting from nothing is not "
+                                      "implemented")
+        if data_init:
+            first = self._batch(next(iter(dataloader)), self.n_components)
+        G.require_hip(self.mu)
+        if data_init:
+            mu, n0 = self.mu.detach().clone(), first.shape[0]
+            mu[:n0] = first
+            if n0 < self.n_components:
+                mu[n0:] = torch.randn_like(mu[n0:]) * torch.std(first, 0, keepdim=True) + torch.mean(first, 0, keepdim=True)
+            self._set_mu(mu)
+        objective = 1e100
+        for step in range(max_iters):
+            weights, mu, cov, objective_new = self._EM_step(dataloader, verbose, cov_regularization)
+            self.set_weights(weights)
+            self._set_mu(mu)
+            self.set_cov(cov)
+            if verbose:
+                print(f"Step {step + 1}, Objective {objective_new:.4f}")
+            if stopping_criterion:
+                if objective - objective_new < stopping_criterion:
+                    return
+            objective = objective_new
 
     # ------------------------------------------------------------------ evaluation
     def _r(self, cov_regularization):

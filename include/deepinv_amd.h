@@ -35,7 +35,7 @@ typedef void* dinv_stream_t; /* hipStream_t */
 /* library / error                                                            */
 /* ------------------------------------------------------------------------- */
 const char* dinv_last_error(void);
-int dinv_version(void);   /* 18 = this header (adds the Gaussian-mixture patch prior: dinv_gmm_scores, dinv_gmm_epll_step and dinv_gmm_epll_workspace_bytes); 17: (adds the ptychography entry points dinv_ptycho_apply and dinv_ptycho_workspace_bytes); 16: (adds the complex64 phase-retrieval entry points dinv_cdense_apply and dinv_cstructured_apply); 15: (adds the DST-I / StructuredRandom entry points dinv_dst1, dinv_structured_apply and the dense fp32 product dinv_dense_apply); 14: (adds dinv_poisson_noise and dinv_fidelity_pointwise); 13: (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
+int dinv_version(void);   /* 19 = this header (adds the EM entry points of the Gaussian mixture: dinv_gmm_posterior, dinv_gmm_moments and dinv_gmm_moments_workspace_bytes); 18: (adds the Gaussian-mixture patch prior: dinv_gmm_scores, dinv_gmm_epll_step and dinv_gmm_epll_workspace_bytes); 17: (adds the ptychography entry points dinv_ptycho_apply and dinv_ptycho_workspace_bytes); 16: (adds the complex64 phase-retrieval entry points dinv_cdense_apply and dinv_cstructured_apply); 15: (adds the DST-I / StructuredRandom entry points dinv_dst1, dinv_structured_apply and the dense fp32 product dinv_dense_apply); 14: (adds dinv_poisson_noise and dinv_fidelity_pointwise); 13: (adds the Walsh-Hadamard entry points dinv_hadamard*); 12: (adds the total-generalized-variation entry points dinv_tgv_*); 11: (adds the DnCNN entry points with bias: dinv_conv3x3_bias, dinv_conv3x3_winograd4_bias, dinv_conv3x3_tail_bias, dinv_bias_grad*); 10: (adds the total-variation entry points dinv_tv_*); 9: (adds dinv_conv_wgrad_3x3x3); 8: (adds dinv_blurfft_apply, dinv_blurfft_workspace_bytes, dinv_spectrum_symbol); 7: (adds dinv_conv3x3_winograd4_last_split, dinv_conv3x3_winograd4_bf16x3, dinv_conv2d/3d_filter_grad, dinv_conv3d*, dinv_cdiv_real, dinv_mask_solve and the dinv_mri_desc.reserved test hook; 6: adds dinv_affine and dinv_conv_down2x2_bf16x3; the parallel-beam Radon entry points stopped reading xn; 5: natural point order in the packed weights of dinv_conv3x3_winograd4; 4: before dinv_conv3x3_winograd4; 3: round 3 before dinv_conv3x3_wsplit; 2: round 2; 1: the round-1 entry points only) */
 /* number of visible HIP devices (0 when no GPU): used by the host to fail loudly */
 int dinv_device_count(int* count);
 
@@ -871,6 +871,27 @@ size_t dinv_gmm_epll_workspace_bytes(int64_t B, int32_t C, int32_t H, int32_t W,
 int dinv_gmm_epll_step(const float* x, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, const float* Wt, const float* m,
                        const float* lam, const float* logw, int32_t K, int32_t d, const float* r, const float* a, const float* cb,
                        const float* bias, float* out, void* workspace, size_t workspace_bytes, dinv_stream_t stream);
+
+/* Expectation-maximisation on rows x [N, d] (GaussianMixtureModel.fit, reference deepinv/optim/utils.py:373-412), three launches
+ * per batch: dinv_gmm_posterior is one, dinv_gmm_moments two (partials, reduce).
+ * dinv_gmm_posterior: the score kernel in rows mode with weights (logw non-null) and r = 0, one launch:
+ *   beta [N, K] the responsibilities exp(score_nk - lse_n), nll [N] = -lse_n, bitwise the NLL epilogue's value of the row.  A lane
+ *   stores its scores in beta and rescales its own row once lse is known; a component whose exp underflows gets exactly 0.
+ * dinv_gmm_moments: for every component the sums over the rows, centred at c [K, d] (the current means; any finite centres do),
+ *   S0_k += sum_n beta_nk,  S1_k += sum_n beta_nk (x_n - c_k),  S2_k += sum_n beta_nk (x_n - c_k)(x_n - c_k)^T,  obj += sum_n nll_n
+ *   into the fp64 device accumulators S0 [K], S1 [K, d], S2 [K, d, d], obj [1], which the caller zeroes before the first batch of an
+ *   EM step.  The rows are cut into chunks of chunk_rows (0: automatic, a function of N, K and d; else a positive multiple of 32);
+ *   every (component, chunk, 32 x 32 output block of the upper triangle of [x - c, 1]^T diag(beta_k) [x - c, 1]) is one fp32
+ *   accumulation on v_mfma_f32_32x32x2_f32, written to the workspace; the reduce launch adds the chunks in ascending order in fp64,
+ *   mirrors the upper triangle (S2 is exactly symmetric) and adds nll in a fixed order.  nll null: obj is left alone (it may then be
+ *   null too).  No atomics: two runs give the same bits.  N = 0 launches nothing and leaves the accumulators as they are.
+ *   The workspace (dinv_gmm_moments_workspace_bytes; 0 for a shape that is refused) must be 16-byte aligned. */
+int dinv_gmm_posterior(const float* x, int64_t N, const float* Wt, const float* m, const float* lam, const float* logw, int32_t K,
+                       int32_t d, float* beta, float* nll, dinv_stream_t stream);
+size_t dinv_gmm_moments_workspace_bytes(int64_t N, int32_t K, int32_t d, int32_t chunk_rows);
+int dinv_gmm_moments(const float* x, const float* beta, const float* c, const float* nll, int64_t N, int32_t K, int32_t d,
+                     int32_t chunk_rows, double* S0, double* S1, double* S2, double* obj, void* workspace, size_t workspace_bytes,
+                     dinv_stream_t stream);
 
 #ifdef __cplusplus
 }
